@@ -8,8 +8,14 @@ float32 -> double), kernel time tile = the reference's BSIZE 1024.
 
 One step = one Filterbank::process() call over 10 s of 48 kHz audio (480,000 samples),
 input already resident in HBM; the result is identical to 469 x {1024-sample block} calls
-(tests/test_filterbank_gpu.py::test_block_split_and_per_sample).  A streaming figure
-(one call per 1024-sample block) is reported beside it.
+(tests/test_filterbank_gpu.py::test_block_split_and_per_sample).
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and
+prints the headline line (metric, value, unit, ms_per_step, ...).  `--dump-outputs DIR` also writes
+the last timed step's output as DIR/y.npy (float64; the input is seeded, so two builds compare
+sample for sample).  `--full` adds every other figure after the timed steps: the profiled pass and
+roofline, the side figures, a streaming figure (one call per 1024-sample block), the per-sample
+rates, the rocprofv3 --pmc child passes and the CPU baseline.
 
 Multi-GPU (one process per GPU): `bench.py --gpus N` outside a launcher reruns itself under
 `torch.distributed.run --nproc-per-node N` as a child process before any torch / HIP import and
@@ -43,6 +49,7 @@ SAMPLES_PER_STEP = 480_000
 FP64_PEAK_TFLOPS = 78.6       # MI355X FP64 vector (= FP64 matrix) peak, SURVEY.md 8(d)
 HBM_PEAK_GBS = 8000.0
 FLOPS_PER_BAND_SAMPLE = 18    # 4*O + 10 with O = 2
+DUMP_MAX_BYTES = 32 << 20     # --dump-outputs: at most this much per rank
 
 
 def c2_coefficients(N=N_BANDS, R=R_POLE):
@@ -740,6 +747,24 @@ def setter_churn_figure(fb, x, y, nb, stream_rate, B=1024, every=4800, nbands=9)
                     "vs_converged_streaming = us_per_block over `streaming`'s converged figure"}
 
 
+def dump_outputs(out_dir, y, rank, world, time_split, first, count):
+    """--dump-outputs: what the last timed process() call returned on this rank, float64.  One
+    GPU: the whole call's mix as y.npy.  N > 1: the time split leaves each rank its own share of
+    the call (y_rank<r>.npy, samples [first, first + count)); the band partition sums the mix to
+    rank 0 (y.npy there).  The step's collectives are complete when this runs (barrier())."""
+    if world > 1 and not time_split and rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    if world > 1 and time_split:
+        name, arr = f"y_rank{rank}.npy", y[first:first + count]
+    else:
+        name, arr = "y.npy", y
+    a = arr.detach().cpu().numpy().astype(np.float64, copy=False)
+    if a.nbytes > DUMP_MAX_BYTES:   # (a long --samples) a fixed, seeded sample of the output
+        a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_BYTES // 8, replace=False))]
+    np.save(os.path.join(out_dir, name), a)
+
+
 def launch_plan(gpus: int, env) -> tuple[str, str | None]:
     """What `bench.py --gpus N` does in this environment (no torch / HIP import before it):
     'run' (world matches), 'relaunch' (N > 1 and no launcher: rerun under torch.distributed.run),
@@ -806,6 +831,12 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--samples", type=int, default=SAMPLES_PER_STEP)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, every other figure: the profiled pass and roofline, the side "
+                         "figures, streaming, per-sample, the rocprofv3 --pmc child passes and the CPU baseline "
+                         "(the --no-* / --side-steps / --stream-blocks options below trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's output (what process() returned) as DIR/<name>.npy")
     ap.add_argument("--stream-blocks", type=int, default=469, help="1024-sample calls for the streaming figure")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-per-sample", action="store_true", help="skip the per-sample drop-in figure")
@@ -848,7 +879,12 @@ def main():
                               "gpus_arg": args.gpus}), flush=True)
         return 0
     if args.workload != "c2":
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs writes the C2 workload's output (--workload c2)")
         return run_row(args)
+    if not args.full:   # a plain run: set up, warm up, time the steps, print the headline line
+        args.no_cpu_baseline = args.no_per_sample = args.no_general_side = args.no_traffic = True
+        args.side_steps = args.stream_blocks = 0
 
     import torch
     import torch.distributed as dist
@@ -998,13 +1034,18 @@ def main():
     t_enq = time.perf_counter() - t0   # host time to issue the steps (launch-bound if ~ elapsed)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ys[(nstep[0] - 1) & 1], rank, world, armed[0], share_first, share_count)
+    seg_ms = mix_ms = red_ms = 0.0
+    launches = 0
     # the engine's GPU time per step (roofline): a separate pass of the same steps with HIP events
     # on the handle's stream (no event records inside the timed region above)
-    fb.profile(True, repeat=8)   # (modal path: each kernel 8x between its events, per-launch times)
-    for _ in range(args.steps):
-        step()
-    barrier()
-    seg_ms, mix_ms, red_ms, launches = fb.profile_read()
+    if args.full:
+        fb.profile(True, repeat=8)   # (modal path: each kernel 8x between its events, per-launch times)
+        for _ in range(args.steps):
+            step()
+        barrier()
+        seg_ms, mix_ms, red_ms, launches = fb.profile_read()
     path = fb.last_path()
     lti = path == HZ_FB_PATH_LTI
     resp = path == HZ_FB_PATH_RESPONSE
@@ -1012,7 +1053,8 @@ def main():
     horizon = fb.response_info()[0]
     modal = bool(resp and fb.modal_info()[3])   # band states by the modal pass (hz_fb_modal.h)
     nexc = max(0, fb.modal_info()[2]) if modal else 0
-    fb.profile(False)
+    if args.full:
+        fb.profile(False)
 
     def timed(fn, warm, steps, n_samples):
         """ms per step and band-samples/s (whole job, max over ranks) of `fn` after `warm` calls"""
@@ -1262,7 +1304,30 @@ def main():
 
     total_band_samples = N_BANDS * S * args.steps
     value = total_band_samples / elapsed
-    if rank == 0:
+    head = {
+        "metric": "band-samples/s (bands x frames/s) for 4096-band Filterbank",
+        "value": value,
+        "unit": "band-samples/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "host_issue_ms_per_step": 1e3 * t_enq / args.steps,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic white noise uniform[-1,1) (float32 -> double), seed 1234, resident in HBM",
+    }
+    if rank == 0 and not args.full:
+        line = {**head,
+                "config": {"workload": "C2 Filterbank<double>(order 2, 4096 bands), resonant band-pass "
+                                       "f_i=0.5(i+1)SR/4096 R=0.999, boost 1 + open, k_p=0.1 k_g=1",
+                           "samples_per_step": S, "samples_per_gpu": share_count if value_split else S,
+                           "bands": N_BANDS, "bands_per_gpu": cnt},
+                "engine": "stationary" if resp else "per-band LTI" if lti else "per-band general"}
+        print(json.dumps(line), flush=True)
+    if rank == 0 and args.full:
         launch_avg_s = (eng_ms_max / 1e3) / max(1, launches)    # whole engine step, per process() call
         # this GPU's outputs per step: its time share (N > 1 / emulated) or the whole call
         out_samples = share_count if value_split else S
@@ -1341,19 +1406,7 @@ def main():
         if not args.no_cpu_baseline:   # rank 0's host cores, at every N (the other ranks wait)
             cpu = cpu_baseline(fwd, back)
         line = {
-            "metric": "band-samples/s (bands x frames/s) for 4096-band Filterbank",
-            "value": value,
-            "unit": "band-samples/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps,
-            "host_issue_ms_per_step": 1e3 * t_enq / args.steps,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic white noise uniform[-1,1) (float32 -> double), seed 1234, resident in HBM",
+            **head,
             "config": {"workload": "C2 Filterbank<double>(order 2, 4096 bands), resonant band-pass "
                                    "f_i=0.5(i+1)SR/4096 R=0.999, boost 1 + open, k_p=0.1 k_g=1",
                        "samples_per_step": S, "samples_per_gpu": out_samples,

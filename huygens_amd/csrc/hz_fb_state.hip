@@ -224,9 +224,12 @@ void fb_state_stamps_dump(const StateArgs& a, int nfft, long call) {
 int fb_state_window(hz_fb* h, const double* x, long len, double* out, hipStream_t st) {
     StateArgs a;
     HZ_TRY(state_args(h, x, len, out, &a));
+    // several pieces: partials only, combined by fb_state_combine_kernel behind the launch (the
+    // kernel boundary makes every piece's partials visible to the combine on any XCD)
+    a.deferred = a.nseg > 1 ? 1 : 0;
     hipLaunchKernelGGL(pick_state(h->order), dim3((unsigned)a.G, (unsigned)a.nseg), dim3(kThreads), 0, st, a);
     HZ_TRY_HIP(hipGetLastError());
-    return HZ_OK;
+    return fb_state_combine(h, a, st);
 }
 
 int fb_state_chained(hz_fb* h, const double* x, long len, double* out, hz_state::StateArgs* a) {
@@ -245,6 +248,8 @@ int fb_state_combine(hz_fb* h, const hz_state::StateArgs& a, hipStream_t st) {
     switch (h->order) {
     case 1: hipLaunchKernelGGL(fb_state_combine_kernel<1>, dim3(grid), dim3(256), 0, st, a); break;
     case 2: hipLaunchKernelGGL(fb_state_combine_kernel<2>, dim3(grid), dim3(256), 0, st, a); break;
+    case 3: hipLaunchKernelGGL(fb_state_combine_kernel<3>, dim3(grid), dim3(256), 0, st, a); break;
+    case 4: hipLaunchKernelGGL(fb_state_combine_kernel<4>, dim3(grid), dim3(256), 0, st, a); break;
     default:
         hz::set_error("fb_state_combine: order %d", h->order);
         return HZ_E_INVALID;

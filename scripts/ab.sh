@@ -14,7 +14,7 @@ i=0
 for setting in "$@"; do
   i=$((i+1))
   [ "$setting" = "-" ] && setting=""
-  env $setting timeout -k 10 120 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-traffic --stream-blocks 0 ${BENCH_ARGS:-} > "$OUT/bench_$i.log" 2>&1
+  env $setting timeout -k 10 120 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-traffic --stream-blocks 0 ${BENCH_ARGS:-} > "$OUT/bench_$i.log" 2>&1
   rc=$?; python3 -c "
 import json
 l=[x for x in open('$OUT/bench_$i.log') if x.startswith('{')]

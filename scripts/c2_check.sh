@@ -11,12 +11,12 @@ if [ -n "$TESTS" ]; then
   rc=$?; tail -3 "$OUT/pytest.log"; echo "pytest rc=$rc"
   [ $rc -ne 0 ] && exit $rc
 fi
-timeout -k 10 300 python -u bench.py --no-cpu-baseline --no-traffic --no-per-sample --side-steps 50 --stream-blocks 469 \
+timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --no-traffic --no-per-sample --side-steps 50 --stream-blocks 469 \
     ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1
 rc=$?; tail -c 3000 "$OUT/bench.log"; echo; echo "bench rc=$rc"
 [ $rc -ne 0 ] && exit $rc
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o trace --output-format csv -- \
-    python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-traffic --no-per-sample --side-steps 0 \
+    python3 bench.py --full --steps 20 --warmup 2 --no-cpu-baseline --no-traffic --no-per-sample --side-steps 0 \
     --stream-blocks 0 ${BENCH_ARGS:-} > "$OUT/prof.log" 2>&1
 rc=$?; echo "rocprof rc=$rc"
 f=$(find "$OUT/prof" -name "*kernel_stats.csv" | head -1)

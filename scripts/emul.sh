@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 2
 export TMPDIR=/tmp
 OUT=gpurun_out/${TAG:-emul}; mkdir -p $OUT
 for w in ${WORLDS:-1 2 4 8}; do
-  timeout -k 10 120 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-traffic --stream-blocks 0 --emulate-world $w > $OUT/ew$w.log 2>&1
+  timeout -k 10 120 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-traffic --stream-blocks 0 --emulate-world $w > $OUT/ew$w.log 2>&1
   rc=$?; python3 -c "
 import json
 l=[x for x in open('$OUT/ew$w.log') if x.startswith('{')]

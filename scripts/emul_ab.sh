@@ -6,7 +6,7 @@ OUT=gpurun_out/${TAG:-emul_ab}; mkdir -p $OUT
 for setting in "$@"; do
   [ "$setting" = "-" ] && setting=""
   for w in ${WORLDS:-8}; do
-    env $setting timeout -k 10 120 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-traffic --stream-blocks 0 --emulate-world $w > $OUT/ew.log 2>&1
+    env $setting timeout -k 10 120 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-traffic --stream-blocks 0 --emulate-world $w > $OUT/ew.log 2>&1
     rc=$?; python3 -c "
 import json
 l=[x for x in open('$OUT/ew.log') if x.startswith('{')]

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/${TAG:-emulweak}
 mkdir -p "$OUT"
 for P in ${WORLDS:-1 2 4 8}; do
-  timeout -k 10 300 python bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-traffic --stream-blocks 0 \
+  timeout -k 10 300 python bench.py --full --steps 100 --warmup 20 --no-cpu-baseline --no-traffic --stream-blocks 0 \
       --side-steps 0 --emulate-world $P > "$OUT/emul_$P.log" 2>&1 || { tail -5 "$OUT/emul_$P.log"; exit 1; }
   python - "$OUT/emul_$P.log" $P <<'PY'
 import json, sys

@@ -5,7 +5,7 @@ OUT=gpurun_out/${TAG:-geom}
 mkdir -p "$OUT"
 for g in ${GEOMS:-"16 1" "8 1" "4 1" "4 2" "4 4"}; do
   set -- $g
-  timeout -k 10 300 python bench.py --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-traffic --stream-blocks 0 \
+  timeout -k 10 300 python bench.py --full --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-traffic --stream-blocks 0 \
       --waves $1 --bands-per-wave $2 > "$OUT/geom_$1_$2.log" 2>&1
   rc=$?
   python3 -c "

@@ -7,7 +7,7 @@ TAG=${TAG:-final} PYTEST_TIMEOUT=600 PYTEST_ARGS="--timeout 300 --timeout-method
     bash scripts/gpu_check.sh || exit $?
 OUT=gpurun_out/${TAG:-final}
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_clean" -o trace --output-format csv -- \
-    python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-traffic --no-per-sample --side-steps 0 \
+    python3 bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-traffic --no-per-sample --side-steps 0 \
     --stream-blocks 0 > "$OUT/prof_clean.log" 2>&1
 rc=$?; echo "clean rocprof rc=$rc"
 exit $rc

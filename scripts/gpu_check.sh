@@ -19,14 +19,14 @@ rc=$?; cat "$OUT/smoke.log" | tail -3; echo "smoke rc=$rc"
 if fatal $rc; then exit $rc; fi
 
 echo "== bench"
-timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1
+timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1
 rc=$?; tail -3 "$OUT/bench.log"; echo "bench rc=$rc"
 if fatal $rc; then exit $rc; fi
 
 if [ -n "${PROFILE-1}" ]; then
   echo "== rocprofv3 kernel trace"
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o trace --output-format csv -- \
-      python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-traffic --stream-blocks 0 > "$OUT/prof.log" 2>&1
+      python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-traffic --stream-blocks 0 > "$OUT/prof.log" 2>&1
   rc=$?; tail -3 "$OUT/prof.log"; echo "rocprof rc=$rc"
   find "$OUT/prof" -name "*stats*" | head
 fi

@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 2
 export TMPDIR=/tmp
 OUT=gpurun_out/${TAG:-pmc}
 mkdir -p "$OUT"
-CMD="python3 bench.py --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline --stream-blocks 0 ${BENCH_ARGS:-}"
+CMD="python3 bench.py --full --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline --stream-blocks 0 ${BENCH_ARGS:-}"
 rocprofv3 -L > "$OUT/counters.txt" 2>&1 || true
 i=0
 for grp in "$@"; do

@@ -9,7 +9,7 @@ IFS=';' read -ra VS <<< "$VARIANTS"
 i=0
 for v in "${VS[@]}"; do
   env $v timeout -k 10 180 rocprofv3 --kernel-trace --stats -d "$OUT/p$i" -o trace --output-format csv -- \
-      python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-traffic --no-per-sample --side-steps 0 \
+      python3 bench.py --full --steps 20 --warmup 2 --no-cpu-baseline --no-traffic --no-per-sample --side-steps 0 \
       --stream-blocks 0 ${BENCH_ARGS:-} > "$OUT/p$i.log" 2>&1 || { echo "variant [$v] failed"; tail -3 "$OUT/p$i.log"; exit 1; }
   f=$(find "$OUT/p$i" -name "*kernel_stats.csv" | head -1)
   echo "== [$v]"

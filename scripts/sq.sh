@@ -10,7 +10,7 @@ for grp in "$@"; do
   i=$((i+1))
   echo "== pass $i: $grp"
   timeout -s KILL 90 rocprofv3 --pmc $grp --kernel-trace -d "$OUT/p$i" -o pmc --output-format csv -- \
-      python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-traffic --stream-blocks 0 ${BENCH_ARGS:-} > "$OUT/p$i.log" 2>&1
+      python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-traffic --stream-blocks 0 ${BENCH_ARGS:-} > "$OUT/p$i.log" 2>&1
   rc=$?; echo "rc=$rc"; tail -2 "$OUT/p$i.log"
   case $rc in 0) ;; *) echo "stop"; exit $rc;; esac
 done

@@ -465,15 +465,10 @@ struct PhaseBank {
             // groups: one task per wave by default.  Fewer groups (a wave taking several tasks in turn)
             // cut the partial rows -- one group writes the output directly, 146 -> 67 MB counted per
             // C3 step -- but measured slower (C3: 19 groups 1.19 ms, 4: 1.46, 2: 1.86; one group for the
-            // long call 1.47 ms: every workgroup then streams all 3.7 MB of partial records per tile);
-            // HZ_ADD_GROUPS sets it (A/B, scripts/r6_c3ab.sh)
+            // long call 1.47 ms: every workgroup then streams all 3.7 MB of partial records per tile)
             const long ntiles = (n + kTile - 1) / kTile;
-            const int gmax = (ntasks + kWaves - 1) / kWaves;
-            int G = gmax;
-            static const int g_env = getenv("HZ_ADD_GROUPS") ? atoi(getenv("HZ_ADD_GROUPS")) : 0;
-            if (g_env > 0) G = std::min(gmax, g_env);
-            const int tpw = (ntasks + G * kWaves - 1) / (G * kWaves);
-            G = (ntasks + tpw * kWaves - 1) / (tpw * kWaves);
+            // (tpw is fixed at 1 here; the kernel's loop over a wave's tasks stays as it is)
+            const int G = (ntasks + kWaves - 1) / kWaves, tpw = 1;
             long nseg = std::max<long>(1, std::min<long>(ntiles, (target_groups + G - 1) / G));
             const long seg_tiles = (ntiles + nseg - 1) / nseg;
             nseg = (ntiles + seg_tiles - 1) / seg_tiles;

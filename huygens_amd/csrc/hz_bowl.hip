@@ -283,9 +283,8 @@ struct ChainArgs {
     int mix;
 };
 
-template <int SPW>
 __global__ __launch_bounds__(kChainThreads) void bowl_dly_chain_kernel(ChainArgs a) {
-    constexpr int kW = kChainThreads / 64;
+    constexpr int SPW = kChainSpw, kW = kChainThreads / 64;
     __shared__ double wsum[kW][SPW];
     __shared__ float xs[SPW];
     __shared__ float ly[(kChainThreads / SPW) * SPW];
@@ -795,16 +794,8 @@ int hz_bowl_fill_delaybank(hz_bowl* h, float* d_buf, hz_dly* bank, void* d_out, 
     a.d = d;
     a.out = (float*)d_out;
     a.mix = mix ? 1 : 0;
-    // samples per workgroup (env HZ_CHAIN_SPW = 2 / 4 / 8 for A/B; lines must fit kChainThreads / SPW)
-    int spw = kChainSpw;
-    if (const char* e = std::getenv("HZ_CHAIN_SPW")) {
-        const int v = std::atoi(e);
-        if ((v == 2 || v == 4 || v == 8) && d.N <= kChainThreads / v) spw = v;
-    }
-    const unsigned grid = (unsigned)((n + spw - 1) / spw);
-    if (spw == 2) hipLaunchKernelGGL(bowl_dly_chain_kernel<2>, dim3(grid), dim3(kChainThreads), 0, h->stream, a);
-    else if (spw == 8) hipLaunchKernelGGL(bowl_dly_chain_kernel<8>, dim3(grid), dim3(kChainThreads), 0, h->stream, a);
-    else hipLaunchKernelGGL(bowl_dly_chain_kernel<kChainSpw>, dim3(grid), dim3(kChainThreads), 0, h->stream, a);
+    const unsigned grid = (unsigned)((n + kChainSpw - 1) / kChainSpw);
+    hipLaunchKernelGGL(bowl_dly_chain_kernel, dim3(grid), dim3(kChainThreads), 0, h->stream, a);
     HZ_TRY_HIP(hipGetLastError());
     if (e) HZ_TRY_HIP(hipEventRecord(e[1], h->stream));
     h->n0 += (double)n;

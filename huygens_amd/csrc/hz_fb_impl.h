@@ -438,8 +438,9 @@ int fb_stream_upkeep(hz_fb* h);        // smoothers and x history over the strea
 int fb_stream_to_hist(hz_fb* h);       // the ring's history back to resp.d_hist (long calls)
 void fb_stream_reset(hz_fb* h);        // state overwritten (set_state, tick)
 void fb_stream_free(hz_fb* h);
-int fb_stream_gain_setter(hz_fb* h);      // a gin-only setter as a streaming transient (0: not applied,
-                                          // 1: applied, d_gin written by its launch)
+int fb_stream_gain_setter(hz_fb* h);      // a gin-only setter as a streaming transient (0: not applicable,
+                                          // 1: applied, d_gin written by its launch, < 0: HZ_E_HIP, a
+                                          // launch failed)
 bool fb_stream_dmode(const hz_fb* h);     // a gain transient is streaming (gains still moving)
 void fb_stream_dclear(hz_fb* h);          // leave the transient mode (the response is rebuilt)
 // the streaming engine's response tail (hz_fb_resp.hip): partition spectra of h[K1, K), and the

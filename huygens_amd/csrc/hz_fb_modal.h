@@ -70,11 +70,10 @@ struct ModalArgs {
     double* exc_part;              // [nexc][chunks][4] (hi, lo) of both components
     int exc_chunks;
     int first2, n2;                // the launch's phase-2 workgroups: blockIdx.x in [first2, first2 + n2)
-    int per1, per2;                // residues r1 per phase-1 workgroup, k1 per phase-2 workgroup
-    int n1, n2p;                   // phase-1 workgroups (128 / per1), phase-2 DFT workgroups (64 / per2)
+    int per1, per2;                // residues r1 per phase-1 workgroup, k1 per phase-2 workgroup: 1 (see
+                                   // phase1_group below)
+    int n1, n2p;                   // phase-1 workgroups (128 / per1), phase-2 DFT workgroups (256 / per2)
     double* out;                   // [N][2]: y[T-1], y[T-2]
-    int first1, n1l;               // the launch's phase-1 (+ exceptional partial) workgroups when they
-                                   // ride in the MAC launch: blockIdx.x in [first1, first1 + n1l)
 };
 
 // (the DFT twiddles are staged in LDS: a global table read inside the MAC loops cost one L2
@@ -247,7 +246,12 @@ __device__ __forceinline__ void phase2(const ModalArgs& a, int w, Lds2& L) {
     for (int i = i0 + t + kThreads; i < i1; i += kThreads) state(a.csr[i], a.par[a.csr[i].x]);
 }
 
-// per1 residues / per2 columns per workgroup, one after the other
+// per1 residues / per2 columns per workgroup, one after the other.  Both counts are 1 (larger ones
+// were measured in round 5 and removed with their switches, commit d5b8cf6); they stay launch
+// arguments because the loop form is what keeps the kernels' schedules: with phase1 / phase2 called
+// directly the compiler issued the operand loads of resp_fwd_kernel's transforms later and those of
+// phase 2 in more dependent rounds (forward 8.27 -> 8.38 us, inverse 7.55 -> 7.95 us per C2 call,
+// alternating runs on one box)
 __device__ __forceinline__ void phase1_group(const ModalArgs& a, int w, Lds1& L) {
     for (int i = 0; i < a.per1; ++i) {
         phase1(a, w * a.per1 + i, L);

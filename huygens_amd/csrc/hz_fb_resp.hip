@@ -32,8 +32,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstdint>
-#include <cstring>
-#include <string>
 
 #include "hz_fb_impl.h"
 #include "hz_fb_state.h"
@@ -246,10 +244,6 @@ union RespLds {
     hz_state::StateLds st;
     hz_modal::Lds2 md;
 };
-union ModalLds {
-    hz_modal::Lds1 m1;
-    hz_modal::Lds2 m2;
-};
 union RespFwdLds {
     hz2k::Lds fft;
     hz_modal::Lds1 m1;
@@ -298,24 +292,8 @@ __global__ __launch_bounds__(kThreads) void resp_fwd_kernel(RespArgs a, hz_modal
 // QP == 0: any Qp, the next block's 2R loads issued before this block's MACs.
 template <int R, int QP>
 __global__ __launch_bounds__(256) void resp_mac_kernel(const double2* __restrict__ H, const double2* __restrict__ Z,
-                                                       double2* __restrict__ Y, int Q, int Qp, int B,
-                                                       hz_modal::ModalArgs md) {
+                                                       double2* __restrict__ Y, int Q, int Qp, int B) {
     constexpr int kBinGroups = kH / 256;
-    if (md.on) {   // modal band states (hz_fb_modal.h): phase 1 and / or phase 2 as extra workgroups
-        __shared__ ModalLds ml;
-        const int i1 = (int)blockIdx.x - md.first1;
-        if (md.n1l && i1 >= 0 && i1 < md.n1l) {
-            if (i1 < md.n1) hz_modal::phase1_group(md, i1, ml.m1);
-            else hz_modal::exc_partial(md, (i1 - md.n1) / md.exc_chunks, (i1 - md.n1) % md.exc_chunks, ml.m2);
-            return;
-        }
-        const int i2 = (int)blockIdx.x - md.first2;
-        if (md.n2 && i2 >= 0 && i2 < md.n2) {
-            if (i2 < md.n2p) hz_modal::phase2_group(md, i2, ml.m2);
-            else hz_modal::exc_sum(md);
-            return;
-        }
-    }
     const int q = (blockIdx.x % kBinGroups) * blockDim.x + threadIdx.x;   // bin
     const int b0 = (blockIdx.x / kBinGroups) * R;
     HZ_DIAG_AT(1, 0);
@@ -395,14 +373,17 @@ __global__ __launch_bounds__(256) void resp_mac_kernel(const double2* __restrict
 // once per 8 blocks and every Z row about four times: 55 MB through the L2s per C2 call, which its
 // operand phase waits 3.4 us for (stamps, profiles/r5/diag); here 20 MB.
 constexpr int kMacBins = 64;
-// BPW output blocks per wave, 4 waves: 4 BPW blocks per workgroup
-template <int QP, int BPW>
-constexpr size_t mac_lds_bytes() { return sizeof(double2) * kMacBins * (QP + 4 * BPW + QP - 1); }
+// kMacBpw output blocks per wave, 4 waves: 32 blocks per workgroup (4 per wave -- 16 per workgroup,
+// twice the workgroups -- measured slower: 8.25 against 6.07 us per C2 launch,
+// profiles/r5/bpw/summary.txt)
+constexpr int kMacBpw = 8;
+template <int QP>
+constexpr size_t mac_lds_bytes() { return sizeof(double2) * kMacBins * (QP + 4 * kMacBpw + QP - 1); }
 
-template <int QP, int BPW>
+template <int QP>
 __global__ __launch_bounds__(256) void resp_mac_kernel_lds(const double2* __restrict__ H, const double2* __restrict__ Z,
                                                            double2* __restrict__ Y, int Q, int B) {
-    constexpr int kMacBlk = 4 * BPW, kZr = kMacBlk + QP - 1, kHL = QP / 4, kZL = (kZr + 3) / 4;
+    constexpr int BPW = kMacBpw, kMacBlk = 4 * BPW, kZr = kMacBlk + QP - 1, kHL = QP / 4, kZL = (kZr + 3) / 4;
     extern __shared__ double2 mac_lds[];
     double2(*hs)[kMacBins] = (double2(*)[kMacBins])mac_lds;
     double2(*zs)[kMacBins] = (double2(*)[kMacBins])(mac_lds + QP * kMacBins);
@@ -471,15 +452,16 @@ __global__ __launch_bounds__(256) void resp_mac_kernel_lds(const double2* __rest
 // for bit.  The register kernel it replaces pulled every H row once per 8 blocks and every Z row
 // ~4 times through the L2s: ~0.5 GB per R = 0.9999 call.
 constexpr int kMacChunk = 24;
-// BINS bins x (256 / BINS) slices of BPW blocks per workgroup: 64 x 4 x 8 = 32 blocks (the C2
-// kernel's tile), 32 x 8 x 8 = 64 or 16 x 16 x 8 = 128 blocks (the default: the H rows re-read by
-// 2 instead of 8 block rows, the Z rows re-read less per block; HZ_MACC_BINS=32 / 64 for A/B)
-template <int BINS, int BPW>
-constexpr size_t macc_lds_bytes() { return sizeof(double2) * BINS * (kMacChunk + (256 / BINS) * BPW + kMacChunk - 1); }
-template <int BINS, int BPW>
+// kMaccBins bins x (256 / kMaccBins) slices of kMacBpw blocks per workgroup: 16 x 16 x 8 = 128 blocks
+// (the H rows re-read by 2 instead of 8 block rows, the Z rows re-read less per block): 35.5 us per
+// R = 0.9999 call against 37.4 (32 x 8 x 8 = 64 blocks) and 46.2 (64 x 4 x 8 = 32 blocks, the C2
+// kernel's tile), alternating on one box (profiles/r6/highq)
+constexpr int kMaccBins = 16;
+constexpr size_t kMaccLdsBytes = sizeof(double2) * kMaccBins * (kMacChunk + (256 / kMaccBins) * kMacBpw + kMacChunk - 1);
 __global__ __launch_bounds__(256) void resp_mac_kernel_ldsc(const double2* __restrict__ H, const double2* __restrict__ Z,
                                                             double2* __restrict__ Y, int Q, int B, int nch, int cps,
                                                             long ystride) {
+    constexpr int BINS = kMaccBins, BPW = kMacBpw;
     constexpr int QP = kMacChunk, SL = 256 / BINS, kMacBlk = SL * BPW, kZr = kMacBlk + QP - 1;
     constexpr int kHL = (QP + SL - 1) / SL, kZL = (kZr + SL - 1) / SL;
     extern __shared__ double2 mac_lds[];
@@ -553,82 +535,41 @@ __global__ __launch_bounds__(256) void resp_mac_kernel_ldsc(const double2* __res
         if (b < B) Y[(long)b * kH + q] = make_double2(ar[r], ai[r]);
     }
 }
-template <int BINS, int BPW>
-void launch_macc_t(int Qp, int B, const double2* H, const double2* Z, double2* Y, int Q, int ns, hipStream_t s) {
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)resp_mac_kernel_ldsc<BINS, BPW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)macc_lds_bytes<BINS, BPW>());
-        attr = true;
-    }
-    constexpr int blk = (256 / BINS) * BPW;
-    const int nch = Qp / kMacChunk, cps = (nch + ns - 1) / ns;
-    const dim3 grid((unsigned)((kH / BINS) * ((B + blk - 1) / blk)), (unsigned)ns);
-    hipLaunchKernelGGL((resp_mac_kernel_ldsc<BINS, BPW>), grid, dim3(256), (macc_lds_bytes<BINS, BPW>()), s, H, Z, Y, Q, B,
-                       nch, cps, (long)B * kH);
-}
 // The long-horizon MAC is latency-bound per chunk (each chunk's operands are fetched one chunk ahead,
-// and a 10 s call gives (kH / BINS) x ceil(B / blk) = 128 workgroups whatever the tile: twice as many,
-// 4 blocks per thread, measured the same 35 us), so the chunks are split over `ns` workgroup planes
-// whose partial sums the inverse launch adds (HZ_MACC_SPLIT = 1 for the unsplit kernel, A/B).  The
-// gain is small (the MAC at 4 planes: 32.5 us), so chunk latency is not what bounds it either
-int macc_splits(int Qp) {
-    static const int env = std::getenv("HZ_MACC_SPLIT") ? std::atoi(std::getenv("HZ_MACC_SPLIT")) : 0;
-    const int nch = Qp / kMacChunk;
-    const int ns = env > 0 ? env : 2;   // R = 0.9999, alternating: 1: 0.0645 / 0.0644, 2: 0.0632 / 0.0628, 4: 0.0640 /
-                                         // 0.0639 ms per call (MAC 35.0 -> 32.5 us, the inverse's sums +1 us)
-    return std::max(1, std::min(ns, nch));
-}
-template <int BINS>
-void launch_macc(int Qp, int B, const double2* H, const double2* Z, double2* Y, int Q, int ns, hipStream_t s) {
-    static const int bpw = std::getenv("HZ_MACC_BPW") ? std::atoi(std::getenv("HZ_MACC_BPW")) : 8;
-    if (bpw == 4) launch_macc_t<BINS, 4>(Qp, B, H, Z, Y, Q, ns, s);
-    else launch_macc_t<BINS, 8>(Qp, B, H, Z, Y, Q, ns, s);
-}
+// and a 10 s call gives (kH / kMaccBins) x ceil(B / blk) = 128 workgroups whatever the tile: twice as
+// many, 4 blocks per thread, measured the same 35 us), so the chunks are split over two workgroup
+// planes whose partial sums the inverse launch adds.  The gain is small (R = 0.9999, alternating: 1
+// plane 0.0645 / 0.0644, 2: 0.0632 / 0.0628, 4: 0.0640 / 0.0639 ms per call; MAC 35.0 -> 32.5 us, the
+// inverse's sums +1 us), so chunk latency is not what bounds it either
+int macc_splits(int Qp) { return std::min(2, Qp / kMacChunk); }
 
-// the LDS-staged MAC for Qp = 8, 16, 24 when no modal phase rides in the MAC launch (C2: 6.1
-// against 7.4 us per launch, step 29.4 against 30.6 us, alternating runs on one box,
-// profiles/r5/mac/summary.txt); HZ_MAC=reg selects the register-only kernel (A/B)
-bool mac_lds_ok(int Qp, bool modal_in_mac) {
-    static const bool reg = [] {
-        const char* v = std::getenv("HZ_MAC");
-        return v && std::strcmp(v, "reg") == 0;
-    }();
-    return !reg && !modal_in_mac && (Qp == 8 || Qp == 16 || Qp == 24 || Qp % kMacChunk == 0);
-}
-template <int BPW>
-void launch_mac_lds_t(int Qp, int B, const double2* H, const double2* Z, double2* Y, int Q, hipStream_t s) {
+// the LDS-staged MAC: Qp = 8, 16, 24 or whole chunks of 24 (q_padded) (C2: 6.1 against 7.4 us per
+// launch of the register-only kernel, step 29.4 against 30.6 us, alternating runs on one box,
+// profiles/r5/mac/summary.txt)
+void launch_mac_lds(int Qp, int B, const double2* H, const double2* Z, double2* Y, int Q, hipStream_t s) {
     static bool attr = false;
     if (!attr) {
-        (void)hipFuncSetAttribute((const void*)resp_mac_kernel_lds<8, BPW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mac_lds_bytes<8, BPW>());
-        (void)hipFuncSetAttribute((const void*)resp_mac_kernel_lds<16, BPW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mac_lds_bytes<16, BPW>());
-        (void)hipFuncSetAttribute((const void*)resp_mac_kernel_lds<24, BPW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mac_lds_bytes<24, BPW>());
+        (void)hipFuncSetAttribute((const void*)resp_mac_kernel_lds<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mac_lds_bytes<8>());
+        (void)hipFuncSetAttribute((const void*)resp_mac_kernel_lds<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mac_lds_bytes<16>());
+        (void)hipFuncSetAttribute((const void*)resp_mac_kernel_lds<24>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mac_lds_bytes<24>());
+        (void)hipFuncSetAttribute((const void*)resp_mac_kernel_ldsc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaccLdsBytes);
         attr = true;
     }
-    const dim3 grid((unsigned)((kH / kMacBins) * ((B + 4 * BPW - 1) / (4 * BPW))));
     if (Qp > kMacChunk) {   // long horizons: partitions in chunks of 24
-        // 16 bins x 128 blocks: 35.5 us per R = 0.9999 call against 37.4 (32 x 64) and 46.2 (64 x 32),
-        // alternating on one box (profiles/r6/highq)
-        static const int bins = std::getenv("HZ_MACC_BINS") ? std::atoi(std::getenv("HZ_MACC_BINS")) : 16;
-        const int ns = macc_splits(Qp);
-        if (bins == 64) launch_macc<64>(Qp, B, H, Z, Y, Q, ns, s);
-        else if (bins == 16) launch_macc<16>(Qp, B, H, Z, Y, Q, ns, s);
-        else launch_macc<32>(Qp, B, H, Z, Y, Q, ns, s);
+        constexpr int blk = (256 / kMaccBins) * kMacBpw;
+        const int ns = macc_splits(Qp), nch = Qp / kMacChunk, cps = (nch + ns - 1) / ns;
+        const dim3 grid((unsigned)((kH / kMaccBins) * ((B + blk - 1) / blk)), (unsigned)ns);
+        hipLaunchKernelGGL(resp_mac_kernel_ldsc, grid, dim3(256), kMaccLdsBytes, s, H, Z, Y, Q, B, nch, cps, (long)B * kH);
         return;
     }
-    if (Qp == 8) hipLaunchKernelGGL((resp_mac_kernel_lds<8, BPW>), grid, dim3(256), (mac_lds_bytes<8, BPW>()), s, H, Z, Y, Q, B);
-    else if (Qp == 16) hipLaunchKernelGGL((resp_mac_kernel_lds<16, BPW>), grid, dim3(256), (mac_lds_bytes<16, BPW>()), s, H, Z, Y, Q, B);
-    else hipLaunchKernelGGL((resp_mac_kernel_lds<24, BPW>), grid, dim3(256), (mac_lds_bytes<24, BPW>()), s, H, Z, Y, Q, B);
-}
-// HZ_MAC_BPW=4: 4 blocks per wave (16 per workgroup, twice the workgroups) -- A/B; measured
-// slower: 8.25 against 6.07 us per C2 launch (profiles/r5/bpw/summary.txt)
-void launch_mac_lds(int Qp, int B, const double2* H, const double2* Z, double2* Y, int Q, hipStream_t s) {
-    static const int bpw = std::getenv("HZ_MAC_BPW") && std::atoi(std::getenv("HZ_MAC_BPW")) == 4 ? 4 : 8;
-    if (bpw == 4) launch_mac_lds_t<4>(Qp, B, H, Z, Y, Q, s);
-    else launch_mac_lds_t<8>(Qp, B, H, Z, Y, Q, s);
+    const dim3 grid((unsigned)((kH / kMacBins) * ((B + 4 * kMacBpw - 1) / (4 * kMacBpw))));
+    if (Qp == 8) hipLaunchKernelGGL(resp_mac_kernel_lds<8>, grid, dim3(256), (mac_lds_bytes<8>()), s, H, Z, Y, Q, B);
+    else if (Qp == 16) hipLaunchKernelGGL(resp_mac_kernel_lds<16>, grid, dim3(256), (mac_lds_bytes<16>()), s, H, Z, Y, Q, B);
+    else hipLaunchKernelGGL(resp_mac_kernel_lds<24>, grid, dim3(256), (mac_lds_bytes<24>()), s, H, Z, Y, Q, B);
 }
 
-typedef void (*MacKernel)(const double2*, const double2*, double2*, int, int, int, hz_modal::ModalArgs);
+// the register-only MAC: the streaming engine's response tail (fb_resp_tail_conv)
+typedef void (*MacKernel)(const double2*, const double2*, double2*, int, int, int);
 MacKernel pick_mac(int Qp) {
     switch (Qp) {
     case 8: return resp_mac_kernel<kMacR, 8>;
@@ -715,7 +656,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) v
     }
     hz2k::Lds& s = u.fft;
     const int t = threadIdx.x;
-    const long b = (long)blockIdx.x - ((SO == 0 && md.on && md.first2 == 0) ? md.n2 : 0);
+    const long b = blockIdx.x;
     if (SO == 0) HZ_DIAG_AT(2, 0);
 #ifdef HZ_DIAG_STAMPS
     long long* stp = SO > 0 && st.stamps ? st.stamps + ((long)st.G * st.nseg + b) * 4 : nullptr;
@@ -1111,13 +1052,9 @@ void modal_args(hz_fb* h, const double* hist, const double* x, long n, double* o
     a->exc_part = R.d_mexc + (size_t)R.mexc_n * (K + 1);
     a->exc_chunks = R.mexc_chunks;
     a->out = out;
-    // (A/B) residues per phase-1 workgroup, columns per phase-2 workgroup
-    static const int per1 = std::getenv("HZ_MODAL_R1PER") ? std::atoi(std::getenv("HZ_MODAL_R1PER")) : 1;
-    static const int per2 = std::getenv("HZ_MODAL_K1PER") ? std::atoi(std::getenv("HZ_MODAL_K1PER")) : 1;
-    a->per1 = (per1 > 0 && kR1 % per1 == 0) ? per1 : 1;
-    a->per2 = (per2 > 0 && kPhase2 % per2 == 0) ? per2 : 1;
-    a->n1 = kR1 / a->per1;
-    a->n2p = kPhase2 / a->per2;
+    a->per1 = a->per2 = 1;
+    a->n1 = kPhase1;
+    a->n2p = kPhase2;
 }
 
 long resp_min_call(const hz_fb* h) { return h->resp.min_call > 0 ? h->resp.min_call : kMinCall; }
@@ -1244,7 +1181,7 @@ int fb_launch_resp(hz_fb* h, const double* d_in, double* d_out, long n) {
         HZ_TRY_HIP(hipMemsetAsync(R.d_Z, 0, sizeof(double) * R.Z_cap, h->stream));
     }
     const size_t zn_at = (size_t)zrows * 2 * kH;   // [zrows] bin kH after the rows
-    const int ys = (mac_lds_ok(Qp, false) && Qp > kMacChunk) ? macc_splits(Qp) : 1;   // (launch_mac_lds's split)
+    const int ys = Qp > kMacChunk ? macc_splits(Qp) : 1;   // (launch_mac_lds's planes)
     HZ_TRY(resp_alloc(&R.d_Y, &R.Y_cap, (size_t)ys * B * kH * 2));
     hipEvent_t* e = nullptr;
     if (h->prof) {
@@ -1299,9 +1236,12 @@ int fb_launch_resp(hz_fb* h, const double* d_in, double* d_out, long n) {
     hz_modal::ModalArgs md = hz_modal::ModalArgs();
     if (modal) modal_args(h, R.d_hist[R.hcur], d_in, n, h->d_ystate[h->scur ^ 1], &md);
     const int so = chained ? h->order : 0;
-    const int nmac = (kH / 256) * ((B + kMacR - 1) / kMacR);
-    int dg_fx = 0, dg_ix = 0, dg_i0 = 0, dg_n1 = 0;   // (diagnostic stamps) modal workgroups per launch
-    (void)dg_fx; (void)dg_ix; (void)dg_i0; (void)dg_n1;
+    // the modal workgroups: phase 1 and the exceptional partials past the forward kernel's nz, phase 2
+    // and the exceptional sums past the inverse kernel's B
+    const int nm1 = modal ? md.n1 + md.nexc * md.exc_chunks : 0;
+    const int nm2 = modal ? md.n2p + (md.nexc ? 1 : 0) : 0;
+    md.first2 = B;
+    md.n2 = nm2;
     R.last_engine = col ? 1 : modal ? 2 : 0;
     R.modal_last = modal;
     if (col) {
@@ -1332,60 +1272,28 @@ int fb_launch_resp(hz_fb* h, const double* d_in, double* d_out, long n) {
                            (const double2*)R.d_T, (const unsigned char*)R.d_cmap, (const double2*)R.d_tw4k, st);
         HZ_TRY_HIP(hipGetLastError());
     } else {
-        // (HZ_MODAL_DIAG, timing diagnostics only -- wrong states: 1 no phase-1 / exceptional
-        // workgroups, 2 no phase 2, 3 no exceptional partials)
-        static const int diag = std::getenv("HZ_MODAL_DIAG") ? std::atoi(std::getenv("HZ_MODAL_DIAG")) : 0;
-        const int nm1 = !modal || diag == 1 ? 0 : diag == 3 ? md.n1 : md.n1 + md.nexc * md.exc_chunks;
-        // phase 1: extra workgroups of the forward kernel (HZ_MODAL_P1=mac: of the MAC kernel -- A/B)
-        static const char* p1env = std::getenv("HZ_MODAL_P1");
-        static const bool p1mac = p1env && std::string(p1env) == "mac";
         // profiling with hz_fb_profile(h, rep > 1): each (idempotent) kernel of the modal path launched rep
         // times between its events
         const int rep = e && modal ? h->prof_rep : 1;
         if (e) h->ev_rep[(e - h->ev.data()) / 5] = (unsigned char)rep;
         for (int r = 0; r < rep; ++r)
-            hipLaunchKernelGGL(resp_fwd_kernel, dim3((unsigned)(nz + (p1mac ? 0 : nm1))), dim3(kThreads), 0,
-                               h->stream, a, md);
+            hipLaunchKernelGGL(resp_fwd_kernel, dim3((unsigned)(nz + nm1)), dim3(kThreads), 0, h->stream, a, md);
         HZ_TRY_HIP(hipGetLastError());
         if (e && inside) {   // profiling: e0..e1 forward, e1..e2 MAC, e2..e4 inverse with the band states
             HZ_TRY_HIP(hipEventRecord(e[1], h->stream));
             h->ev_skip[(e - h->ev.data()) / 5] &= (unsigned char)~2;
         }
-        // phase 2: extra workgroups of the inverse kernel after its transforms (HZ_MODAL_P2 =
-        // inv_first: before them; mac: beside the MAC -- A/B)
-        static const char* p2env = std::getenv("HZ_MODAL_P2");
-        static const int p2 = !p2env ? 1 : std::string(p2env) == "mac" ? 0 : std::string(p2env) == "inv_first" ? 2 : 1;
-        const int nm2 = !modal || diag == 2 ? 0 : md.n2p + (md.nexc ? 1 : 0);
-        hz_modal::ModalArgs mdm = md, mdi = md;
-        mdm.on = modal && (p2 == 0 || p1mac);
-        mdm.first2 = nmac;
-        mdm.n2 = p2 == 0 ? nm2 : 0;
-        mdm.first1 = nmac + mdm.n2;
-        mdm.n1l = modal && p1mac ? nm1 : 0;
-        mdi.on = modal && p2 != 0;
-        mdi.first2 = p2 == 2 ? 0 : B;
-        mdi.n2 = nm2;
-        a.ys = (mac_lds_ok(Qp, mdm.on) && Qp > kMacChunk) ? macc_splits(Qp) : 1;   // launch_mac_lds's planes
-        for (int r = 0; r < rep; ++r) {
-            if (mac_lds_ok(Qp, mdm.on))
-                launch_mac_lds(Qp, B, (const double2*)R.d_H, (const double2*)R.d_Z, (double2*)R.d_Y, Q, h->stream);
-            else
-                hipLaunchKernelGGL(pick_mac(Qp), dim3((unsigned)(nmac + (mdm.on ? mdm.n2 + mdm.n1l : 0))), dim3(256), 0,
-                                   h->stream, (const double2*)R.d_H, (const double2*)R.d_Z, (double2*)R.d_Y, Q, Qp, B, mdm);
-        }
+        for (int r = 0; r < rep; ++r)
+            launch_mac_lds(Qp, B, (const double2*)R.d_H, (const double2*)R.d_Z, (double2*)R.d_Y, Q, h->stream);
         HZ_TRY_HIP(hipGetLastError());
         if (e && inside) {
             HZ_TRY_HIP(hipEventRecord(e[2], h->stream));
             h->ev_skip[(e - h->ev.data()) / 5] |= 8;
         }
-        dg_fx = p1mac ? 0 : nm1;
-        dg_n1 = md.n1;
-        dg_ix = mdi.on ? nm2 : 0;
-        dg_i0 = mdi.first2;
         RespKernel ki = so == 1 ? resp_inv_kernel<1> : so == 2 ? resp_inv_kernel<2> : resp_inv_kernel<0>;
         for (int r = 0; r < rep; ++r)
-            hipLaunchKernelGGL(ki, dim3((unsigned)(B + (chained ? st.G * st.nseg : 0) + (mdi.on ? nm2 : 0))),
-                               dim3(kThreads), 0, h->stream, a, st, mdi);
+            hipLaunchKernelGGL(ki, dim3((unsigned)(B + (chained ? st.G * st.nseg : 0) + nm2)), dim3(kThreads), 0,
+                               h->stream, a, st, md);
         HZ_TRY_HIP(hipGetLastError());
     }
     if (chained) HZ_TRY(fb_state_combine(h, st, h->stream));   // pieces of a small bank
@@ -1417,14 +1325,15 @@ int fb_launch_resp(hz_fb* h, const double* d_in, double* d_out, long n) {
         static long long hv[3][1024][4];
         if (hipMemcpyFromSymbol(hv, HIP_SYMBOL(g_diag), sizeof(hv)) == hipSuccess) {
             // workgroups [0, main) run the kernel's own part, the rest (up to 1024) the modal phases
-            const int tot[3] = {std::min((int)nz + dg_fx, 1024), std::min(nmac, 1024), std::min((int)B + dg_ix, 1024)};
+            const int nmac = (kH / 256) * ((B + kMacR - 1) / kMacR);
+            const int tot[3] = {std::min((int)nz + nm1, 1024), std::min(nmac, 1024), std::min((int)B + nm2, 1024)};
             for (int k = 0; k < 3; ++k) {
                 long long t0 = hv[k][0][0];
                 for (int i = 0; i < tot[k]; ++i) t0 = std::min(t0, hv[k][i][0]);
                 double ph[3] = {0, 0, 0}, emain = 0, eextra = 0, smax = 0;
                 int nmain = 0, nextra = 0;
                 for (int i = 0; i < tot[k]; ++i) {
-                    const bool extra = k == 0 ? i >= nz : k == 2 ? (dg_i0 == 0 ? i < dg_ix : i >= B) : false;
+                    const bool extra = k == 0 ? i >= nz : k == 2 ? i >= B : false;
                     const double e = (hv[k][i][3] - t0) * 0.01;
                     smax = std::max(smax, (hv[k][i][0] - t0) * 0.01);
                     if (extra) {
@@ -1436,15 +1345,15 @@ int fb_launch_resp(hz_fb* h, const double* d_in, double* d_out, long n) {
                         for (int j = 0; j < 3; ++j) ph[j] += (hv[k][i][j + 1] - hv[k][i][j]) * 0.01;
                     }
                 }
-                if (k == 0 && dg_fx > dg_n1) {   // phase-1 residues vs the exceptional bands' partials
+                if (k == 0 && nm1 > hz_modal::kPhase1) {   // phase-1 residues vs the exceptional bands' partials
                     double e1 = 0, ex = 0;
                     for (int i = nz; i < tot[0]; ++i) {
                         const double e = (hv[0][i][3] - t0) * 0.01;
-                        if (i < nz + dg_n1) e1 = std::max(e1, e);
+                        if (i < nz + hz_modal::kPhase1) e1 = std::max(e1, e);
                         else ex = std::max(ex, e);
                     }
                     std::fprintf(stderr, "[fwd stamps] phase-1 workgroups (%d) last end %.2f us, exceptional partials (%d) last end %.2f us\n",
-                                 dg_n1, e1, dg_fx - dg_n1, ex);
+                                 hz_modal::kPhase1, e1, nm1 - hz_modal::kPhase1, ex);
                 }
                 std::fprintf(stderr, "[%s stamps] %d workgroups: mean operands %.2f us, compute %.2f us, stores %.2f us; "
                              "starts up to %.2f us, last end %.2f us; %d modal workgroups, last end %.2f us\n",
@@ -1531,7 +1440,7 @@ int fb_resp_tail_conv(hz_fb* h, const double* u, long n, double* out, hipStream_
     HZ_TRY_HIP(hipGetLastError());
     const int nmac = (kH / 256) * ((B + kMacR - 1) / kMacR);
     hipLaunchKernelGGL(pick_mac(Qp), dim3((unsigned)nmac), dim3(256), 0, st, (const double2*)S.d_tH,
-                       (const double2*)S.d_tZ, (double2*)S.d_tY, Q, Qp, B, hz_modal::ModalArgs());
+                       (const double2*)S.d_tZ, (double2*)S.d_tY, Q, Qp, B);
     HZ_TRY_HIP(hipGetLastError());
     hipLaunchKernelGGL(resp_inv_kernel<0>, dim3((unsigned)B), dim3(kThreads), 0, st, a, hz_state::StateArgs(),
                        hz_modal::ModalArgs());

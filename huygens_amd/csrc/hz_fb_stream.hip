@@ -685,7 +685,6 @@ struct SetterArgs {
     const double* line;
     long last;
     double* xhist;
-    int skip;             // (diagnostic, HZ_SETTER_SKIP: bit 0 columns, 1 taps, 2 upkeep return at once)
     unsigned long long* trace;    // (diagnostic, HZ_STREAM_TRACE) [2][512]: every workgroup's start and end
 };
 
@@ -736,7 +735,6 @@ __device__ __forceinline__ void setter_roles(const SetterArgs& a, SetterLds& u, 
 #pragma unroll
     for (int e = 0; e < kChurnArg; ++e) lb[e] = a.L.band[e];
     if ((int)vblk >= kCols + nt) {   // upkeep
-        if (a.skip & 4) return;
         const int b = (vblk - kCols - nt) * kT + t;
         if (b < a.N) {
             double gb = a.gin[b];
@@ -756,7 +754,6 @@ __device__ __forceinline__ void setter_roles(const SetterArgs& a, SetterLds& u, 
         return;
     }
     if ((int)vblk >= kCols) {   // taps: 256 of partition tp (uniform over the workgroup)
-        if (a.skip & 2) return;
         const long tau = (long)(vblk - kCols) * kT + t;
         const int tp = (int)(tau / kSP), tj = (int)(tau % kSP);
         const double hv = a.h[tau], hdv = a.dfirst ? 0.0 : a.hD[tau];
@@ -800,7 +797,6 @@ __device__ __forceinline__ void setter_roles(const SetterArgs& a, SetterLds& u, 
         return;
     }
     // column c
-    if (a.skip & 1) return;
     const int c = vblk, l = t & 63, w = t >> 6, j = l & 31, g = 2 * w + (l >> 5);
     // everything that does not depend on the setter's bands, in flight first
     double2 z1[QI], z3[QI], hs[QI], hd[QI];
@@ -825,7 +821,7 @@ __device__ __forceinline__ void setter_roles(const SetterArgs& a, SetterLds& u, 
     for (int i = 0; i < QI; ++i) dS[i] = zero2;
     const int QO = Q * O, n2 = (O + 1) * 32;
     COL_MARK(0)
-    for (int q0 = 0; q0 < ((a.skip & 8) ? 0 : mq); q0 += kSetBatch) {
+    for (int q0 = 0; q0 < mq; q0 += kSetBatch) {
         const int nb = min(kSetBatch, mq - q0), nS = nb * QO, nP = nb * n2;
         long bl[kSetBatch];
 #pragma unroll
@@ -894,7 +890,10 @@ __device__ __forceinline__ void setter_roles(const SetterArgs& a, SetterLds& u, 
         __syncthreads();
     }
     COL_MARK(2)
-    if (a.skip & 16) return;
+    // (never taken: fb_stream_gain_setter launches no empty list.  The uniform test ends the band loop's
+    // block here, as the diagnostic return that stood here did; without it the register allocator
+    // spills more inside that loop at QI = 16: 480 against 468 B of scratch per lane)
+    if (mq <= 0) return;
     double2 y = zero2, r = zero2;
 #pragma unroll
     for (int i = 0; i < QI; ++i) {
@@ -940,18 +939,6 @@ __global__ __launch_bounds__(kT) void stream_setter_kernel(SetterArgs a) {
     __shared__ SetterLds u;
     if (a.trace && threadIdx.x == 0) a.trace[blockIdx.x] = __builtin_amdgcn_s_memrealtime();
     setter_roles<QI>(a, u, (int)blockIdx.x);
-    if (a.trace) {
-        __syncthreads();
-        if (threadIdx.x == 0) a.trace[512 + blockIdx.x] = __builtin_amdgcn_s_memrealtime();
-    }
-}
-
-// (A/B, HZ_SETTER_SPLIT=1) the taps and upkeep roles as a kernel of their own, without the column
-// workgroups' LDS (the column kernel then runs kCols workgroups)
-__global__ __launch_bounds__(kT) void stream_setter_taps_kernel(SetterArgs a) {
-    extern __shared__ double no_lds[];
-    if (a.trace && threadIdx.x == 0) a.trace[blockIdx.x] = __builtin_amdgcn_s_memrealtime();
-    setter_roles<1>(a, *reinterpret_cast<SetterLds*>(no_lds), kCols + (int)blockIdx.x);
     if (a.trace) {
         __syncthreads();
         if (threadIdx.x == 0) a.trace[512 + blockIdx.x] = __builtin_amdgcn_s_memrealtime();
@@ -1223,10 +1210,7 @@ unsigned long long* trace_slot(hz_fb* h, int kind) {
     if (S.trace_n == kTraceN) trace_flush(h);
     const int i = S.trace_n++;
     S.trace_kind[i] = kind;
-    static const bool split = getenv("HZ_SETTER_SPLIT") && atoi(getenv("HZ_SETTER_SPLIT"));
-    S.trace_wg[i] = kind == 3   ? (int)(S.K1 / kT + (h->N + kT - 1) / kT)
-                    : kind == 2 ? (split ? kCols : (int)(kCols + S.K1 / kT + (h->N + kT - 1) / kT))
-                                : (kind == 1 ? kBlockWGD : kBlockWG);
+    S.trace_wg[i] = kind == 2 ? (int)(kCols + S.K1 / kT + (h->N + kT - 1) / kT) : (kind == 1 ? kBlockWGD : kBlockWG);
     return S.d_trace + (size_t)i * 1024;
 }
 
@@ -1454,7 +1438,8 @@ void fb_stream_dclear(hz_fb* h) {
 // responses' spectra and the C / R parities of the next block move by linearity in the same launch
 // (stream_setter_kernel, which also brings the smoothers up to date: fb_upload skips its upkeep).
 // Returns 0: not applicable here (the caller invalidates the response as before); 1: applied, d_gin
-// written by the update launch (no host copy, no synchronisation).
+// written by the update launch (no host copy, no synchronisation); HZ_E_HIP (negative): a launch
+// failed -- the update may be half applied, so the caller gives up instead of rebuilding from it.
 int fb_stream_gain_setter(hz_fb* h) {
     hz_fb::Resp& R = h->resp;
     hz_fb::Resp::Stream& S = R.st;
@@ -1536,7 +1521,7 @@ int fb_stream_gain_setter(hz_fb* h) {
         }
         hipLaunchKernelGGL(stream_rspec_kernel, dim3(kCols, (unsigned)(O + 1), (unsigned)N), dim3(kT), 0, h->stream,
                            (const double*)S.d_r0, (const double*)S.d_phi, O, (const double2*)S.d_tw, (double2*)S.d_rsp);
-        if (hipGetLastError() != hipSuccess) return 0;
+        HZ_TRY_HIP(hipGetLastError());
         S.rband_valid = true;
     }
     const bool dfirst = !S.dmode;
@@ -1579,10 +1564,7 @@ int fb_stream_gain_setter(hz_fb* h) {
         sa.sp_m = (double)powl((long double)h->sp, (long double)S.pend);
         sa.sg_m = (double)powl((long double)h->sg, (long double)S.pend);
         sa.last = ring_index(S, S.pos - 1) + S.R;
-        S.pend = 0;
     }
-    static const int skip = getenv("HZ_SETTER_SKIP") ? atoi(getenv("HZ_SETTER_SKIP")) : 0;
-    sa.skip = skip;
     sa.trace = trace_slot(h, 2);
     const unsigned wg = (unsigned)(kCols + K / kT + (N + kT - 1) / kT);
     for (size_t i = 0; i < lists.size(); ++i) {   // (later lists: h_D already rebased, upkeep done)
@@ -1592,25 +1574,10 @@ int fb_stream_gain_setter(hz_fb* h) {
             sa.dfirst = 0;
             sa.upkeep = 0;
         }
-        static const bool split = getenv("HZ_SETTER_SPLIT") && atoi(getenv("HZ_SETTER_SPLIT"));
-        if (split) {
-            SetterArgs st = sa;
-            st.trace = trace_slot(h, 3);
-            hipLaunchKernelGGL(stream_setter_taps_kernel, dim3(wg - kCols), dim3(kT), 0, h->stream, st);
-            hipLaunchKernelGGL(pick_setter(Q / 8), dim3(kCols), dim3(kT), 0, h->stream, sa);
-        } else {
-            // (diagnostic, HZ_SETTER_TWICE=1: the same launch twice -- wrong results, the second
-            // launch's trace shows the cost with its code and operands warm)
-            static const bool twice = getenv("HZ_SETTER_TWICE") && atoi(getenv("HZ_SETTER_TWICE"));
-            if (twice) {
-                SetterArgs s1 = sa;
-                s1.trace = trace_slot(h, 2);
-                hipLaunchKernelGGL(pick_setter(Q / 8), dim3(wg), dim3(kT), 0, h->stream, s1);
-            }
-            hipLaunchKernelGGL(pick_setter(Q / 8), dim3(wg), dim3(kT), 0, h->stream, sa);
-        }
+        hipLaunchKernelGGL(pick_setter(Q / 8), dim3(wg), dim3(kT), 0, h->stream, sa);
     }
-    if (hipGetLastError() != hipSuccess) return 0;
+    HZ_TRY_HIP(hipGetLastError());
+    S.pend = 0;   // (the first launch brought the smoothers up to date)
     S.dmax = rebase * S.dmax + dmx;
     S.dref = S.pos;
     S.dmode = true;

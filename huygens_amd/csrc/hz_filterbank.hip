@@ -644,6 +644,7 @@ int fb_upload(hz_fb* h) {
     // also brings the smoothers up to date and writes d_gin)
     const int transient = (h->dirty_gin && !h->dirty_pin && !h->dirty_coef && !h->tv_pending)
                               ? hz_fbi::fb_stream_gain_setter(h) : 0;
+    if (transient < 0) HZ_TRY(transient);   // a launch failed: nothing below runs on the half-applied update
     // streamed samples bring the smoothers up to date lazily, toward the targets they ran with:
     // apply them before new targets (mix / boost) reach the device
     if (!transient && (h->dirty_pin || h->dirty_gin)) HZ_TRY(hz_fbi::fb_stream_upkeep(h));

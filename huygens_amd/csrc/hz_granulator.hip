@@ -60,7 +60,6 @@ struct GranArgs {
     unsigned size, o0;    // Buffer size and origin at time T0
     unsigned long fm;     // fastmod multiplier for `size`: 2^64 / size rounded up (0 for size 1)
     unsigned wrap1;       // (2^32 - 1) % size: the second tap's slot when the first index is 0 mod 2^32
-    int fastcos;          // cos_0_2pi for the window (HZ_GRAN_LIBCOS=1: the library cos, A/B)
 };
 
 // x mod size for any uint32 x, without a divide (Lemire, Kaser & Kurz 2019, "fastmod")
@@ -132,7 +131,7 @@ __global__ __launch_bounds__(kThreads) void gran_kernel(GranArgs a) {
                 phase = tk / g.sizes;
             }
             const double arg = 2 * hz::kPI * phase;
-            const double cv = hz_rt::hann_cos(arg, a.fastcos != 0);
+            const double cv = hz_rt::hann_cos(arg);
             const double term = g.gains * src * (0.5 * (1 - cv));   // wave.h:148
             if (act[u]) out += term;
         }
@@ -326,8 +325,6 @@ int gran_run(hz_gran* h, const double* d_in, double* d_out, long n, const hz_gra
         a.o0 = (unsigned)(T0 % (long)h->size);
         a.fm = h->size == 1u ? 0ul : ~0ul / h->size + 1ul;
         a.wrap1 = 0xffffffffu % h->size;
-        static const bool libcos = std::getenv("HZ_GRAN_LIBCOS") != nullptr;
-        a.fastcos = libcos ? 0 : 1;
         hipEvent_t* e = nullptr;
         if (h->prof) {
             if (h->ev_used + 2 > h->ev.size())

@@ -103,8 +103,8 @@ __device__ __forceinline__ void sincos_0_2pi(double x, double* sn_out, double* c
 }
 
 // the Granulator's window term's cosine, block kernel and per-sample server alike (bit-identical)
-__device__ __forceinline__ double hann_cos(double arg, bool fast) {
-    return (fast && arg >= 0.0 && arg <= 6.2831853072) ? cos_0_2pi(arg) : cos(arg);
+__device__ __forceinline__ double hann_cos(double arg) {
+    return (arg >= 0.0 && arg <= 6.2831853072) ? cos_0_2pi(arg) : cos(arg);
 }
 
 // ---- op arguments (copied into the request line; <= kArgWords 8-byte words) ------------------

@@ -484,16 +484,15 @@ __device__ __forceinline__ void cmul_fma(double& r, double& i, double2 w, bool c
     i = ni;
 }
 
-// Twiddles once per element (an A/B alternative; the stage-wise form below is the default): a radix-8 DIF group {base + j d} (p its offset in the span) is the
-// 8-point DFT of its elements followed by W_N^(e r) on output j, r = bitrev3(j), e = p 2^(lg-1-lh);
-// the DIT group mirrors it (conj W_N^(e r) on input j, e = p 2^(lg-3-lh), then the butterflies).
-// The stage-by-stage form (hz::dif_regs / dit_regs) multiplied every stage's differences: 12
-// complex products per group and pass against 7 here.  Host-built tables after the N/2 table
-// (hz_stft_create), contiguous in p: A[r-1][p] = W^(p r), p < 512 (forward lh 11, inverse lh 9);
-// B[r-1][p] = W^(8 p r), p < 64 (lh 8 / 6); C[r-1][p] = W^(64 p r), p < 8 (lh 5 / 3); lh 2 / 0 have
-// p = 0 (no twiddles).  A thread's 21 twiddles load once.
+// The pass twiddles of a radix-8 group {base + j d} (p its offset in the span): host-built tables
+// after the N/2 table (hz_stft_create), contiguous in p: A[r-1][p] = W^(p r), p < 512 (forward lh 11,
+// inverse lh 9); B[r-1][p] = W^(8 p r), p < 64 (lh 8 / 6); C[r-1][p] = W^(64 p r), p < 8 (lh 5 / 3);
+// lh 2 / 0 have p = 0 (no twiddles).  The stage-by-stage groups below read rows r = 1, 2, 4.  (Rows
+// r <= 7 serve twiddles applied once per element, after the 8-point DFT of a DIF group / before a
+// DIT group's: 7 complex products per group and pass against 12, yet measured slower on one box,
+// 15.1 vs 14.6 us per C4 step, alternating runs, profiles/r4/rows/c4/ab.log; measured in round 4 and
+// removed, its code is in commit d5b8cf6.)
 constexpr int kTwA = 0, kTwB = 7 * 512, kTwC = kTwB + 7 * 64, kTwLen = kTwC + 7 * 8;
-constexpr int kBr3[8] = {0, 4, 2, 6, 1, 5, 3, 7};
 
 // the stage-by-stage form (hz::dif_regs<3, true> order: stage k's differences times W^(e 2^k))
 template <bool UNIT>
@@ -529,54 +528,6 @@ __device__ __forceinline__ void dit8s(double (&xr)[8], double (&xi)[8], const do
             if (j & S) continue;
             double cr = xr[j + S], ci = xi[j + S];
             if (!UNIT) cmul_fma(cr, ci, w, true);
-            hz::mul_root16(cr, ci, (j & (S - 1)) << (3 - k), true);
-            const double ar = xr[j], ai = xi[j];
-            xr[j] = ar + cr;
-            xi[j] = ai + ci;
-            xr[j + S] = ar - cr;
-            xi[j + S] = ai - ci;
-        }
-    }
-}
-
-// radix-8 DIF group: butterflies with the pass-internal roots, then the output twiddles
-template <bool UNIT>
-__device__ __forceinline__ void dif8(double (&xr)[8], double (&xi)[8], const double2 (&tw)[7]) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int S = 8 >> (k + 1);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if (j & S) continue;
-            const double ar = xr[j], ai = xi[j], cr = xr[j + S], ci = xi[j + S];
-            double dr = ar - cr, di = ai - ci;
-            hz::mul_root16(dr, di, (j & (S - 1)) << (1 + k), false);
-            xr[j] = ar + cr;
-            xi[j] = ai + ci;
-            xr[j + S] = dr;
-            xi[j + S] = di;
-        }
-    }
-    if (!UNIT) {
-#pragma unroll
-        for (int j = 1; j < 8; ++j) cmul_fma(xr[j], xi[j], tw[kBr3[j] - 1], false);
-    }
-}
-
-// radix-8 DIT group: the input twiddles (conjugate), then the butterflies with the internal roots
-template <bool UNIT>
-__device__ __forceinline__ void dit8(double (&xr)[8], double (&xi)[8], const double2 (&tw)[7]) {
-    if (!UNIT) {
-#pragma unroll
-        for (int j = 1; j < 8; ++j) cmul_fma(xr[j], xi[j], tw[kBr3[j] - 1], true);
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int S = 1 << k;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if (j & S) continue;
-            double cr = xr[j + S], ci = xi[j + S];
             hz::mul_root16(cr, ci, (j & (S - 1)) << (3 - k), true);
             const double ar = xr[j], ai = xi[j];
             xr[j] = ar + cr;
@@ -743,7 +694,7 @@ __device__ __forceinline__ void gate(double2* zf, double p0, double p1, double* 
 }
 }  // namespace p4
 
-template <int PROC, bool ONCE>
+template <int PROC>
 __global__ __launch_bounds__(p4::kT) void stft_pair4096_kernel(StftArgs a, long nf) {
 #pragma clang fp contract(off)
     using namespace p4;
@@ -795,37 +746,37 @@ __global__ __launch_bounds__(p4::kT) void stft_pair4096_kernel(StftArgs a, long 
             xi[j] = w[j] * v1[j];
         }
     }
-    if constexpr (ONCE) dif8<false>(xr, xi, twA); else dif8s<false>(xr, xi, twA);   // lh 11
+    dif8s<false>(xr, xi, twA);   // lh 11
     lds_put<512>(z, dif_base<9>(b), xr, xi);
     __syncthreads();
     lds_get<64>(z, dif_base<6>(b), xr, xi);
-    if constexpr (ONCE) dif8<false>(xr, xi, twB); else dif8s<false>(xr, xi, twB);   // lh 8
+    dif8s<false>(xr, xi, twB);   // lh 8
     lds_put<64>(z, dif_base<6>(b), xr, xi);
     wave_sync();
     lds_get<8>(z, dif_base<3>(b), xr, xi);
-    if constexpr (ONCE) dif8<false>(xr, xi, twC); else dif8s<false>(xr, xi, twC);   // lh 5
+    dif8s<false>(xr, xi, twC);   // lh 5
     lds_put<8>(z, dif_base<3>(b), xr, xi);
     wave_sync();
     lds_get<1>(z, dif_base<0>(b), xr, xi);
-    if constexpr (ONCE) dif8<true>(xr, xi, twC); else dif8s<true>(xr, xi, twC);   // lh 2
+    dif8s<true>(xr, xi, twC);   // lh 2
     lds_put<1>(z, dif_base<0>(b), xr, xi);
     __syncthreads();
     gate<PROC>(z, a.p0, a.p1, scratch);
     __syncthreads();
     lds_get<1>(z, dit_base<0>(b), xr, xi);
-    if constexpr (ONCE) dit8<true>(xr, xi, twC); else dit8s<true>(xr, xi, twC);   // lh 0
+    dit8s<true>(xr, xi, twC);   // lh 0
     lds_put<1>(z, dit_base<0>(b), xr, xi);
     wave_sync();
     lds_get<8>(z, dit_base<3>(b), xr, xi);
-    if constexpr (ONCE) dit8<false>(xr, xi, twC); else dit8s<false>(xr, xi, twC);   // lh 3
+    dit8s<false>(xr, xi, twC);   // lh 3
     lds_put<8>(z, dit_base<3>(b), xr, xi);
     wave_sync();
     lds_get<64>(z, dit_base<6>(b), xr, xi);
-    if constexpr (ONCE) dit8<false>(xr, xi, twB); else dit8s<false>(xr, xi, twB);   // lh 6
+    dit8s<false>(xr, xi, twB);   // lh 6
     lds_put<64>(z, dit_base<6>(b), xr, xi);
     __syncthreads();
     lds_get<512>(z, dit_base<9>(b), xr, xi);
-    if constexpr (ONCE) dit8<false>(xr, xi, twA); else dit8s<false>(xr, xi, twA);   // lh 9
+    dit8s<false>(xr, xi, twA);   // lh 9
     // natural order {b + 512 j}: straight to the ring (the Re planes only, as stft_pair_kernel)
     double* o0 = a.fo + row0 * kN;
     double* o1 = a.fo + row1 * kN;
@@ -834,310 +785,6 @@ __global__ __launch_bounds__(p4::kT) void stft_pair4096_kernel(StftArgs a, long 
         o0[b + kT * j] = xr[j];
         if (two) o1[b + kT * j] = xi[j];
     }
-}
-
-// ---- N = 4096, one real frame per workgroup (StaticSTFT's gate on real input; C4) ------------------
-// The frame's 4096 real samples as 2048 complex ones, z[n] = w x[2n] + i w x[2n+1] (fourier.h:110-112
-// windowing), so the transform is a 2048-point one on 256 threads (4 waves, 32 KB of LDS): twice the
-// workgroups of the pair kernel at half the size, two or more resident per CU, where the pair kernel
-// ran one 8-wave workgroup per CU and exposed every pass's barrier and LDS round trip.
-//   forward: Z = DFT_M(z), M = N/2; per bin pair (k, M - k): E = (Z_k + conj Z_{M-k}) / 2,
-//            O = (Z_k - conj Z_{M-k}) / 2i, t = W_N^k O, X_k = E + t, X_{M-k} = conj(E - t)
-//            (bins N - k are conj X_k; bin 0 and M from Z_0, bin M/2 = conj Z_{M/2})
-//   gate:    the reference's per-bin test on |X_k|^2 against p0 avg^2 (staticSTFT.h:99-128, or the
-//            gate625 callback), avg over all N bins
-//   inverse: Z''_k = S + V, Z''_{M-k} = conj(S - V), S = X'_k + conj X'_{M-k}, V = i conj(W_N^k)
-//            (X'_k - conj X'_{M-k}); z'' = IDFT_M(Z''), y[2n] + i y[2n+1] = z''[n] (unnormalised, as
-//            FFTW's backward transform; the overlap-add divides)
-// Pass plan: DIF lh 10-9-8 (stride 256), 7-6-5 (32), 4-3-2 (4), 1-0 (radix 4, contiguous); the
-// inverse mirrored. Twiddles W_{8s}^{p r} of a stride-s pass are W_N^{(N/8s) p r} of the N/2 table.
-// The layout p4::lx is conflict-free for every pass (scripts/probe/stft_layout_half.py).
-namespace h4 {
-constexpr int kM = 2048, kLgM = 11, kT = 256, kN = 4096;
-inline size_t lds_bytes() { return sizeof(double2) * kM + sizeof(double) * 16; }
-
-// the last forward pass: stages lh 1, 0 on two radix-4 groups of contiguous elements
-__device__ __forceinline__ void dif4x2(double (&xr)[8], double (&xi)[8]) {
-#pragma unroll
-    for (int g = 0; g < 8; g += 4) {
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {   // h = 2: the difference times W_4^e
-            const double ar = xr[g + e], ai = xi[g + e], cr = xr[g + e + 2], ci = xi[g + e + 2];
-            const double dr = ar - cr, di = ai - ci;
-            xr[g + e] = ar + cr;
-            xi[g + e] = ai + ci;
-            if (e == 0) {
-                xr[g + 2] = dr;
-                xi[g + 2] = di;
-            } else {   // (dr + i di)(-i)
-                xr[g + 3] = di;
-                xi[g + 3] = -dr;
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; e += 2) {   // h = 1
-            const double ar = xr[g + e], ai = xi[g + e], cr = xr[g + e + 1], ci = xi[g + e + 1];
-            xr[g + e] = ar + cr;
-            xi[g + e] = ai + ci;
-            xr[g + e + 1] = ar - cr;
-            xi[g + e + 1] = ai - ci;
-        }
-    }
-}
-
-// the first inverse pass: stages lh 0, 1 (DIT: the second input times conj W_4^e)
-__device__ __forceinline__ void dit4x2(double (&xr)[8], double (&xi)[8]) {
-#pragma unroll
-    for (int g = 0; g < 8; g += 4) {
-#pragma unroll
-        for (int e = 0; e < 4; e += 2) {   // h = 1
-            const double ar = xr[g + e], ai = xi[g + e], cr = xr[g + e + 1], ci = xi[g + e + 1];
-            xr[g + e] = ar + cr;
-            xi[g + e] = ai + ci;
-            xr[g + e + 1] = ar - cr;
-            xi[g + e + 1] = ai - ci;
-        }
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {   // h = 2
-            double cr = xr[g + e + 2], ci = xi[g + e + 2];
-            if (e == 1) {   // (cr + i ci) i
-                const double t = cr;
-                cr = -ci;
-                ci = t;
-            }
-            const double ar = xr[g + e], ai = xi[g + e];
-            xr[g + e] = ar + cr;
-            xi[g + e] = ai + ci;
-            xr[g + e + 2] = ar - cr;
-            xi[g + e + 2] = ai - ci;
-        }
-    }
-}
-
-// a stride-s pass's stage twiddles for dif8s / dit8s (entries 0, 1, 3 = W_{8s}^{p}, ^{2p}, ^{4p})
-template <int F>   // F = N / (8 s)
-__device__ __forceinline__ void pass_tw(const double2* __restrict__ tw, int p, double2 (&t)[7]) {
-    t[0] = tw[F * p];
-    t[1] = tw[2 * F * p];
-    t[3] = tw[4 * F * p];
-    t[2] = t[4] = t[5] = t[6] = make_double2(1.0, 0.0);
-}
-
-// split, gate and merge over spectrum positions (p4::gate's walk at lg = 11)
-template <int PROC>
-__device__ __forceinline__ void gate(double2* zf, const double2* __restrict__ tw, double p0, double p1,
-                                     double* scratch) {
-#pragma clang fp contract(off)
-    constexpr int kItems = 5;   // 1023 pairs, then u = 1023 (bins 0 and M) and u = 1024 (bin M/2)
-    const int b = threadIdx.x;
-    double er[kItems], ei[kItems], tr[kItems], ti[kItems], wr[kItems], wi[kItems];
-    int ek[kItems], em[kItems], kind[kItems];   // kind 0 pair, 1 bins 0 / M, 2 bin M/2, 3 none
-    double pa = 0.0, la = 0.0;
-#pragma unroll
-    for (int i = 0; i < kItems; ++i) {
-        const int u = b + kT * i;
-        kind[i] = u < kM / 2 - 1 ? 0 : u == kM / 2 - 1 ? 1 : u == kM / 2 ? 2 : 3;
-        er[i] = ei[i] = tr[i] = ti[i] = wr[i] = wi[i] = 0.0;
-        ek[i] = em[i] = 0;
-        if (kind[i] == 3) continue;
-        double xa_r, xa_i, xb_r = 0.0, xb_i = 0.0, ca, cb;   // the item's bins and their counts
-        if (kind[i] == 0) {
-            const int q = (u + 1) + p4::hibit(u + 1), qq = q ^ (p4::hibit(q) - 1);
-            const int kq = hz::bitrev(q, kLgM), kqq = hz::bitrev(qq, kLgM);
-            const int k = kq < kqq ? kq : kqq;
-            ek[i] = p4::lx(kq < kqq ? q : qq);
-            em[i] = p4::lx(kq < kqq ? qq : q);
-            const double2 zk = zf[ek[i]], zm = zf[em[i]], w = tw[k];
-            wr[i] = w.x;
-            wi[i] = w.y;
-            er[i] = (zk.x + zm.x) * 0.5;
-            ei[i] = (zk.y - zm.y) * 0.5;
-            const double orr = (zk.y + zm.y) * 0.5, oi = (zm.x - zk.x) * 0.5;
-            tr[i] = w.x * orr - w.y * oi;   // t = W^k O
-            ti[i] = w.x * oi + w.y * orr;
-            xa_r = er[i] + tr[i];   // X_k
-            xa_i = ei[i] + ti[i];
-            xb_r = er[i] - tr[i];   // X_{M-k} = conj(E - t)
-            xb_i = -(ei[i] - ti[i]);
-            ca = cb = 2.0;
-        } else if (kind[i] == 1) {
-            ek[i] = p4::lx(0);
-            const double2 z0 = zf[ek[i]];
-            er[i] = z0.x;   // E_0, O_0
-            tr[i] = z0.y;
-            xa_r = z0.x + z0.y;   // X_0
-            xa_i = 0.0;
-            xb_r = z0.x - z0.y;   // X_M
-            ca = cb = 1.0;
-        } else {
-            ek[i] = p4::lx(1);
-            const double2 zh = zf[ek[i]];
-            xa_r = zh.x;   // X_{M/2} = conj Z_{M/2}
-            xa_i = -zh.y;
-            ca = 2.0;
-            cb = 0.0;
-        }
-        er[i] = kind[i] == 0 ? er[i] : xa_r;   // kinds 1, 2 keep the bins themselves
-        ei[i] = kind[i] == 0 ? ei[i] : xa_i;
-        tr[i] = kind[i] == 0 ? tr[i] : xb_r;
-        ti[i] = kind[i] == 0 ? ti[i] : xb_i;
-        if constexpr (PROC == HZ_PROC_STATIC_GATE) {
-            pa += ca * (sqrt(xa_r * xa_r + xa_i * xa_i) / kN);
-            if (cb != 0.0) pa += cb * (sqrt(xb_r * xb_r + xb_i * xb_i) / kN);
-        } else {
-            const double ha = hypot(xa_r, xa_i), hb = hypot(xb_r, xb_i);
-            hz::dd_add(pa, la, ha);
-            if (ca == 2.0) hz::dd_add(pa, la, ha);
-            if (cb != 0.0) hz::dd_add(pa, la, hb);
-            if (cb == 2.0) hz::dd_add(pa, la, hb);
-        }
-    }
-    double thr;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if constexpr (PROC == HZ_PROC_STATIC_GATE) {   // staticSTFT.h:99-128
-        for (int o = 32; o > 0; o >>= 1) pa += __shfl_xor(pa, o, 64);
-        if (lane == 0) scratch[wave] = pa;
-        __syncthreads();
-        double avg = 0.0;
-        for (int w = 0; w < kT / 64; ++w) avg += scratch[w];
-        thr = p0 * avg * avg;
-    } else {   // tests/spectral.cpp:32-72 (sum / N in long double)
-        for (int o = 32; o > 0; o >>= 1) {
-            const double ah = __shfl_xor(pa, o, 64), al = __shfl_xor(la, o, 64);
-            hz::dd_add(pa, la, ah);
-            hz::dd_add(pa, la, al);
-        }
-        if (lane == 0) {
-            scratch[2 * wave] = pa;
-            scratch[2 * wave + 1] = la;
-        }
-        __syncthreads();
-        pa = la = 0.0;
-        for (int w = 0; w < kT / 64; ++w) {
-            hz::dd_add(pa, la, scratch[2 * w]);
-            hz::dd_add(pa, la, scratch[2 * w + 1]);
-        }
-        const double qa = pa / kN;
-        const double avg = qa + (fma(-qa, (double)kN, pa) + la) / kN;
-        thr = p0 * avg * avg;
-    }
-    auto gated = [&](double& xr, double& xi) {
-        if constexpr (PROC == HZ_PROC_STATIC_GATE) {
-            if (xr * xr + xi * xi < thr) {
-                xr = xr * p1;
-                xi = xi * p1;
-            }
-        } else {
-            if (!(xr * xr + xi * xi > thr)) xr = xi = 0.0;
-        }
-    };
-#pragma unroll
-    for (int i = 0; i < kItems; ++i) {
-        if (kind[i] == 3) continue;
-        if (kind[i] == 0) {
-            double ar = er[i] + tr[i], ai = ei[i] + ti[i];      // X_k
-            double br = er[i] - tr[i], bi = -(ei[i] - ti[i]);   // X_{M-k}
-            gated(ar, ai);
-            gated(br, bi);
-            // S = X'_k + conj X'_{M-k}, D = X'_k - conj X'_{M-k}, V = i conj(W^k) D
-            const double sr = ar + br, si = ai - bi, dr = ar - br, di = ai + bi;
-            const double cr = wr[i] * dr + wi[i] * di, ci = wr[i] * di - wi[i] * dr;   // conj(W^k) D
-            const double vr = -ci, vi = cr;
-            zf[ek[i]] = make_double2(sr + vr, si + vi);
-            zf[em[i]] = make_double2(sr - vr, -(si - vi));
-        } else if (kind[i] == 1) {
-            double ar = er[i], ai = 0.0, br = tr[i], bi = 0.0;
-            gated(ar, ai);
-            gated(br, bi);
-            zf[ek[i]] = make_double2(ar + br, ar - br);
-        } else {
-            double ar = er[i], ai = ei[i];
-            gated(ar, ai);
-            zf[ek[i]] = make_double2(2.0 * ar, -2.0 * ai);
-        }
-    }
-}
-}  // namespace h4
-
-template <int PROC>
-__global__ __launch_bounds__(h4::kT) void stft_half4096_kernel(StftArgs a, long nf) {
-#pragma clang fp contract(off)
-    using namespace h4;
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    double2* z = (double2*)lds;
-    double* scratch = lds + 2 * kM;
-    const int b = threadIdx.x;
-    double2 twA[7], twB[7], twC[7];
-    pass_tw<2>(a.tw, b, twA);          // stride 256
-    pass_tw<16>(a.tw, b & 31, twB);    // stride 32
-    pass_tw<128>(a.tw, b & 3, twC);    // stride 4
-    const int fl = frame_of_block(blockIdx.x, gridDim.x);
-    long off, row;
-    if (a.sh_world <= 1) {
-        const int tl = 2 * a.laps;
-        const int j0 = a.i0 + fl;
-        const int c0 = j0 / tl;
-        off = a.u0 + (long)c0 * (2 * kN - 1) + (long)a.stride * (j0 - c0 * tl);
-        row = (a.r0 + fl) % a.R;
-    } else {
-        const long f = frame_at(a, fl);
-        off = frame_start(f, a.laps, a.stride, kN) - a.T0 + (kN - 1);
-        row = f % a.R;
-    }
-    (void)nf;
-    double xr[8], xi[8];
-    {   // z[n] = w x[2n] + i w x[2n+1], n = b + 256 j (fourier.h:110-112)
-        double v0[8], v1[8];
-        double2 w[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int n = b + kT * j;
-            const long u = off + 2 * n;   // position in [history (N-1) | block input]
-            v0[j] = u < kN - 1 ? a.hr[u] : a.inr[u - (kN - 1)];
-            v1[j] = u + 1 < kN - 1 ? a.hr[u + 1] : a.inr[u + 1 - (kN - 1)];
-            w[j] = ((const double2*)a.win)[n];
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            xr[j] = w[j].x * v0[j];
-            xi[j] = w[j].y * v1[j];
-        }
-    }
-    p4::dif8s<false>(xr, xi, twA);   // lh 10, 9, 8
-    p4::lds_put<256>(z, b, xr, xi);
-    __syncthreads();
-    p4::lds_get<32>(z, p4::dif_base<5>(b), xr, xi);
-    p4::dif8s<false>(xr, xi, twB);   // lh 7, 6, 5
-    p4::lds_put<32>(z, p4::dif_base<5>(b), xr, xi);
-    p4::wave_sync();
-    p4::lds_get<4>(z, p4::dif_base<2>(b), xr, xi);
-    p4::dif8s<false>(xr, xi, twC);   // lh 4, 3, 2
-    p4::lds_put<4>(z, p4::dif_base<2>(b), xr, xi);
-    p4::wave_sync();
-    p4::lds_get<1>(z, 8 * b, xr, xi);
-    dif4x2(xr, xi);                  // lh 1, 0
-    p4::lds_put<1>(z, 8 * b, xr, xi);
-    __syncthreads();
-    gate<PROC>(z, a.tw, a.p0, a.p1, scratch);
-    __syncthreads();
-    p4::lds_get<1>(z, 8 * b, xr, xi);
-    dit4x2(xr, xi);                  // lh 0, 1
-    p4::lds_put<1>(z, 8 * b, xr, xi);
-    p4::wave_sync();
-    p4::lds_get<4>(z, p4::dit_base<2>(b), xr, xi);
-    p4::dit8s<false>(xr, xi, twC);   // lh 2, 3, 4
-    p4::lds_put<4>(z, p4::dit_base<2>(b), xr, xi);
-    p4::wave_sync();
-    p4::lds_get<32>(z, p4::dit_base<5>(b), xr, xi);
-    p4::dit8s<false>(xr, xi, twB);   // lh 5, 6, 7
-    p4::lds_put<32>(z, p4::dit_base<5>(b), xr, xi);
-    __syncthreads();
-    p4::lds_get<256>(z, b, xr, xi);
-    p4::dit8s<false>(xr, xi, twA);   // lh 8, 9, 10
-    // natural order z''[b + 256 j] = y[2n] + i y[2n + 1]: straight to the ring's Re plane
-    double2* o = (double2*)(a.fo + row * kN);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[b + kT * j] = make_double2(xr[j], xi[j]);
 }
 
 struct OlaArgs {
@@ -1248,8 +895,10 @@ __global__ __launch_bounds__(256) void stft_ola_kernel(OlaArgs a) {
 // run in the reference's slot order (ascending i). The last N - 1 inputs are carried into the
 // next call's history by the first `aux` workgroups, which also write the zeros before the first
 // frame completes.
-template <int LAPS, int SPLIT>   // SPLIT workgroups per segment
+constexpr int kOlaSplit = 2;   // workgroups per segment
+template <int LAPS>
 __global__ __launch_bounds__(256) void stft_ola_seg_kernel(OlaArgs a, long g0, long u_lo, long u_hi, int aux) {
+    constexpr int SPLIT = kOlaSplit;
     constexpr int S = 2 * LAPS;
     constexpr int SPT = 16 / LAPS / SPLIT > 0 ? 16 / LAPS / SPLIT : 1;   // samples per thread per round
     const int N = a.N, stride = a.stride;
@@ -1590,33 +1239,15 @@ void launch_pairs(hz_stft* h, const StftArgs& a, long nf) {
                                   (int)frame_lds(kMaxN));
         attr = true;
     }
-    static const bool generic = std::getenv("HZ_STFT_GENERIC_PAIR") != nullptr;   // (A/B measurements)
-    // twiddles once per element (7 products per group and pass) measured slower on one box than the
-    // stage-wise form (12): 15.1 vs 14.6 us per C4 step, alternating runs (profiles/r4/rows/c4/ab.log);
-    // HZ_STFT_TWIDDLE_ONCE=1 selects it for such A/B runs
-    static const bool stagewise = std::getenv("HZ_STFT_TWIDDLE_ONCE") == nullptr;
-    // HZ_STFT_FRAME=half: one frame per workgroup (2048-point even/odd transform); pair (default):
-    // two frames per 4096-point transform -- for A/B runs
-    static const bool pair4096 = [] {
-        const char* v = std::getenv("HZ_STFT_FRAME");
-        return !(v && std::strcmp(v, "half") == 0);
-    }();
-    if (h->N == h4::kN && !generic && !pair4096) {
-        hipLaunchKernelGGL((stft_half4096_kernel<PROC>), dim3((unsigned)nf), dim3(h4::kT), h4::lds_bytes(),
-                           h->stream, a, nf);
-    } else if (h->N == p4::kN && !generic) {
+    if (h->N == p4::kN) {
         static bool attr4 = false;
         if (!attr4) {
-            for (const void* k : {(const void*)stft_pair4096_kernel<PROC, true>, (const void*)stft_pair4096_kernel<PROC, false>})
-                (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p4::lds_bytes());
+            (void)hipFuncSetAttribute((const void*)stft_pair4096_kernel<PROC>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)p4::lds_bytes());
             attr4 = true;
         }
-        if (stagewise)
-            hipLaunchKernelGGL((stft_pair4096_kernel<PROC, false>), dim3((unsigned)((nf + 1) / 2)), dim3(p4::kT),
-                               p4::lds_bytes(), h->stream, a, nf);
-        else
-            hipLaunchKernelGGL((stft_pair4096_kernel<PROC, true>), dim3((unsigned)((nf + 1) / 2)), dim3(p4::kT),
-                               p4::lds_bytes(), h->stream, a, nf);
+        hipLaunchKernelGGL((stft_pair4096_kernel<PROC>), dim3((unsigned)((nf + 1) / 2)), dim3(p4::kT), p4::lds_bytes(),
+                           h->stream, a, nf);
     } else if (frame_rmax(h->N) == 3)
         hipLaunchKernelGGL((stft_pair_kernel<PROC, 3>), dim3((unsigned)((nf + 1) / 2)), dim3(frame_threads(h->N)),
                            frame_lds(h->N), h->stream, a, nf);
@@ -1778,8 +1409,7 @@ int stft_block(hz_stft* h, const double* d_re, const double* d_im, double* d_ore
     o.sh_rank = h->sh_rank;
     o.sh_inv = 1.0 / (double)h->sh_block;
     o.im_zero_from = h->im_zero_from;
-    static const bool ola_flat = std::getenv("HZ_STFT_OLA_FLAT") != nullptr;   // (A/B measurements)
-    if (!ola_flat && (h->laps == 2 || h->laps == 4 || h->laps == 8) && h->stride * h->laps == N) {
+    if ((h->laps == 2 || h->laps == 4 || h->laps == 8) && h->stride * h->laps == N) {
         // segment overlap-add: one workgroup per stride-long segment of the period grid
         const long P = 2L * N - 1, S = 2L * h->laps;
         const long u_lo = std::max(h->T - (N - 1), 0L), u_hi = h->T + n - 1 - (N - 1);
@@ -1793,23 +1423,13 @@ int stft_block(hz_stft* h, const double* d_re, const double* d_im, double* d_ore
         const long nseg = u_hi >= u_lo ? seg(u_hi) - g0 + 1 : 0;
         const long zp = h->T < N - 1 ? std::min((long)N - 1, h->T + n) - h->T : 0;
         const int aux = (int)((std::max((long)N - 1, zp) + 255) / 256);
-        // (diagnostics) HZ_STFT_OLA_REPEAT=r launches the idempotent overlap-add r times: the later
-        // launches show its time with the ring already in the L2s
-        static const int ola_rep = std::max(1, std::getenv("HZ_STFT_OLA_REPEAT") ? std::atoi(std::getenv("HZ_STFT_OLA_REPEAT")) : 1);
-        // two workgroups per segment by default (7.4 against 7.8 us per C4 launch, alternating runs,
-        // profiles/r5/c4_half/olasplit.txt); HZ_STFT_OLA_SPLIT=1|2|4 for A/B runs
-        static const int split = [] {
-            const char* v = std::getenv("HZ_STFT_OLA_SPLIT");
-            const int x = v ? std::atoi(v) : 2;
-            return x == 1 || x == 4 ? x : 2;
-        }();
-        const dim3 gridS((unsigned)(aux + split * nseg));
-        for (int rep = 0; rep < ola_rep; ++rep) {
-            auto go = [&](auto kern) { hipLaunchKernelGGL(kern, gridS, dim3(256), 0, h->stream, o, g0, u_lo, u_hi, aux); };
-            if (h->laps == 2) split == 1 ? go(stft_ola_seg_kernel<2, 1>) : split == 2 ? go(stft_ola_seg_kernel<2, 2>) : go(stft_ola_seg_kernel<2, 4>);
-            else if (h->laps == 4) split == 1 ? go(stft_ola_seg_kernel<4, 1>) : split == 2 ? go(stft_ola_seg_kernel<4, 2>) : go(stft_ola_seg_kernel<4, 4>);
-            else split == 1 ? go(stft_ola_seg_kernel<8, 1>) : split == 2 ? go(stft_ola_seg_kernel<8, 2>) : go(stft_ola_seg_kernel<8, 4>);
-        }
+        // two workgroups per segment (7.4 against 7.8 us per C4 launch with one, alternating runs,
+        // profiles/r5/c4_half/olasplit.txt)
+        const dim3 gridS((unsigned)(aux + kOlaSplit * nseg));
+        auto go = [&](auto kern) { hipLaunchKernelGGL(kern, gridS, dim3(256), 0, h->stream, o, g0, u_lo, u_hi, aux); };
+        if (h->laps == 2) go(stft_ola_seg_kernel<2>);
+        else if (h->laps == 4) go(stft_ola_seg_kernel<4>);
+        else go(stft_ola_seg_kernel<8>);
     } else {
         const long threads = std::max(n, (long)N - 1);
         hipLaunchKernelGGL(stft_ola_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->stream, o);

@@ -24,6 +24,13 @@
 // exceptional: a direct dot product of the window with their own response (host, long double),
 // accumulated in double-double per 16384-sample chunk (phase 1) and summed in phase 2.
 // numpy model and CPU checks: tests/modal_model.py, tests/test_modal_model_cpu.py.
+//
+// LDS layout: both phases' DFT loops read their tables at lane-dependent strides, and a CU's modal
+// workgroup shares the LDS pipe with the transform workgroup beside it.  The tables are padded
+// (px, px1 below; bank model: tests/test_modal_lds_layout_cpu.py) -- the same values in the same
+// order.  Measured at C2: SQ_LDS_BANK_CONFLICT of the inverse launch 687k -> 85k
+// cycles (these reads, not the transform's, were its conflicts) and the launch 7.3 -> 6.9 us; of the
+// forward launch 147k -> 100k, time unchanged.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -78,15 +85,27 @@ struct ModalArgs {
 
 // (the DFT twiddles are staged in LDS: a global table read inside the MAC loops cost one L2
 // latency per unrolled batch -- phase 2 took ~19 us that way)
+// phase 1's twiddle table is padded by one element per 32: the two lanes (h = 0, 1) of an output
+// read W64^((32 h + i) k1), elements 32 apart for odd k1 -- unpadded, the same bank group two rows
+// apart; with px1 one bank group on (the model in tests/test_modal_lds_layout_cpu.py counts the rows)
+constexpr int kPad1 = kR2 + kR2 / 32;   // 66
+__device__ __forceinline__ constexpr int px1(int e) { return e + (e >> 5); }
 struct Lds1 {
     double red[4][64][2];
     double F[2][64];
-    double2 w64[kR2];
+    double2 w64[kPad1];
 };
+// phase 2's operand tables are padded by one 16-byte element per 16 (a bank row: 64 banks x 4 B):
+// the eight lanes of an output read elements 16 qq + i (a) and ((16 qq + i) k2) & 127 (w128), whose
+// index mod 16 does not depend on qq -- unpadded, eight rows of one bank group; padded, element e of
+// row e >> 4 sits in bank group (e + (e >> 4)) & 15, so the rows' groups differ (lanes that share a
+// row share the address).  tests/test_modal_lds_layout_cpu.py models it.
+constexpr int kPad = kR1 + kR1 / 16;   // 136
+__device__ __forceinline__ constexpr int px(int e) { return e + (e >> 4); }
 struct Lds2 {
-    double2 a[2][kR1];
+    double2 a[2][kPad];
     double2 g[2][kR1];
-    double2 w128[kR1];
+    double2 w128[kPad];
     hz_dd::dd part[kThreads][2];
 };
 
@@ -100,7 +119,7 @@ __device__ __forceinline__ double win(const ModalArgs& a, long i) { return i < a
 __device__ __forceinline__ void phase1(const ModalArgs& a, int r1, Lds1& L) {
     const int t = threadIdx.x, r2 = t & 63, g = t >> 6;
     const int r = r1 + kR1 * r2;
-    if (t < kR2) L.w64[t] = a.tw[kR1 * t];   // W64^t
+    if (t < kR2) L.w64[px1(t)] = a.tw[kR1 * t];   // W64^t
     const double2 wr = a.tw[(r1 * ((t >> 1) & 63)) & (kL - 1)];   // W^(r1 k1) of this thread's output
     const double w0 = a.wR[r];
     double f0 = 0.0, f1 = 0.0;
@@ -124,7 +143,7 @@ __device__ __forceinline__ void phase1(const ModalArgs& a, int r1, Lds1& L) {
         double re = 0.0, im = 0.0;
 #pragma unroll 8
         for (int q = 32 * h; q < 32 * h + 32; ++q) {
-            const double2 w = L.w64[(q * k1) & 63];   // W64^(q k1)
+            const double2 w = L.w64[px1((q * k1) & 63)];   // W64^(q k1)
             const double f = L.F[j][q];
             re = fma(f, w.x, re);
             im = fma(f, w.y, im);
@@ -201,8 +220,8 @@ __device__ __forceinline__ void phase2(const ModalArgs& a, int w, Lds2& L) {
     const double x1 = win(a, a.K - 1), x2 = win(a, a.K - 2), x3 = win(a, a.K - 3);
     {
         const int j = t >> 7, r1 = t & 127;
-        L.a[j][r1] = a.A[((long)j * kR2 + k1) * kR1 + r1];
-        if (t < kR1) L.w128[t] = a.tw[kR2 * t];   // W128^t
+        L.a[j][px(r1)] = a.A[((long)j * kR2 + k1) * kR1 + r1];
+        if (t < kR1) L.w128[px(t)] = a.tw[kR2 * t];   // W128^t
     }
     __syncthreads();
     {
@@ -211,8 +230,8 @@ __device__ __forceinline__ void phase2(const ModalArgs& a, int w, Lds2& L) {
         double re = 0.0, im = 0.0;
 #pragma unroll 8
         for (int r1 = 16 * qq; r1 < 16 * qq + 16; ++r1) {
-            const double2 wv = L.w128[(r1 * k2) & 127];   // W128^(r1 k2)
-            const double2 v = L.a[j][r1];
+            const double2 wv = L.w128[px((r1 * k2) & 127)];   // W128^(r1 k2)
+            const double2 v = L.a[j][px(r1)];
             re = fma(v.x, wv.x, re);
             re = fma(-v.y, wv.y, re);
             im = fma(v.x, wv.y, im);

@@ -61,6 +61,50 @@ constexpr long kBandsPerSample = 256;
 // changed nothing)
 static_assert(kH == hz2k::kN && kThreads == hz2k::kT, "hz_fft2k.h: 2048 points on 256 threads");
 
+// 16-byte stores of what the next launch (Z, Y) or the caller (out) reads, through one helper with
+// a policy per buffer.  kStThrough: write-through (sc1) buffer stores -- the bytes leave the
+// producer's L2 while other workgroups still compute, instead of in the write-back after the
+// launch's last workgroup.  The descriptor's base is the workgroup's own row / block (wave-uniform:
+// kernel arguments and blockIdx only), so offsets and the record count stay far below 2^31 for any
+// call length, and a store past `bytes` is dropped by the range check.  Narrow (8-byte) stores stay
+// plain: write-through is one fabric write per store whatever its width.  The macros are the A/B
+// hooks (one build per policy set); DESIGN.md 3.6 has the measurements behind the defaults.
+enum StorePolicy { kStPlain = 0, kStThrough = 1 };
+#ifndef HZ_ST_Z
+#define HZ_ST_Z kStThrough
+#endif
+#ifndef HZ_ST_Y
+#define HZ_ST_Y kStThrough
+#endif
+#ifndef HZ_ST_OUT
+#define HZ_ST_OUT kStThrough
+#endif
+constexpr int kStZ = HZ_ST_Z;       // window spectra: resp_fwd_kernel (the stationary step and the streaming tail)
+constexpr int kStY = HZ_ST_Y;       // output spectra: the LDS-staged MACs
+constexpr int kStOut = HZ_ST_OUT;   // the call's output: resp_inv_kernel's aligned 16-byte stores
+#ifndef HZ_ST_UPKEEP
+#define HZ_ST_UPKEEP kStPlain
+#endif
+constexpr int kStUpkeep = HZ_ST_UPKEEP;   // resp_upkeep's 8-byte stores (history, smoothers, x history)
+typedef unsigned int hz_u32x4 __attribute__((ext_vector_type(4)));
+template <int POL>
+struct Store16 {
+    double2* base;
+    __amdgpu_buffer_rsrc_t rs;
+    __device__ __forceinline__ Store16(double2* b, unsigned bytes) : base(b) {
+        if constexpr (POL == kStThrough) rs = __builtin_amdgcn_make_buffer_rsrc(b, 0, bytes, 0x00020000);
+    }
+    __device__ __forceinline__ void operator()(unsigned i, double2 v) const {   // base[i] = v
+        if constexpr (POL == kStThrough) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(hz_u32x4, v), rs, 16u * i, 0, 16);
+        else base[i] = v;
+    }
+};
+template <int POL>
+__device__ __forceinline__ void store8(double* p, double v) {   // kStThrough: an 8-byte sc1 store
+    if constexpr (POL == kStThrough) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else *p = v;
+}
+
 #ifdef HZ_DIAG_STAMPS
 // (diagnostic builds) per-workgroup stamps of the forward [0] and MAC [1] kernels: start, operands
 // arrived, transform / MACs done, end
@@ -137,7 +181,8 @@ __global__ __launch_bounds__(256) void resp_hsum_kernel(const double* __restrict
 // one thread per pair (k, kH - k), k = t + 256 i (k = 0 pairs with itself: X_0 and X_kH; thread
 // 0 also takes k = kH / 2).  Rows hold X_0 .. X_{kH-1} (X_0 real, imaginary part 0); X_kH (real)
 // is kept apart (nyq), so the MAC is one complex product per stored bin.
-template <class Load>
+// (POL: the row's store policy)
+template <int POL, class Load>
 __device__ __forceinline__ void real_window_fwd(hz2k::Lds& s, Load load, const double2* __restrict__ tw,
                                                 double2* __restrict__ zrow, double* __restrict__ nyq,
                                                 bool stamps = false) {
@@ -165,6 +210,7 @@ __device__ __forceinline__ void real_window_fwd(hz2k::Lds& s, Load load, const d
 #endif
     hz2k::fwd(s, vr, vi, ft);   // ends with a barrier
     if (stamps) HZ_DIAG_AT(0, 2);
+    const Store16<POL> zst(zrow, kH * (unsigned)sizeof(double2));
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int k = t + i * kThreads, kb = (kH - k) & (kH - 1);
@@ -173,13 +219,13 @@ __device__ __forceinline__ void real_window_fwd(hz2k::Lds& s, Load load, const d
         const double er = 0.5 * (ar + br), ei = 0.5 * (ai - bi);
         const double orr = 0.5 * (ai + bi), oi = -0.5 * (ar - br);
         const double wr = w[i].x * orr - w[i].y * oi, wi = w[i].x * oi + w[i].y * orr;
-        zrow[k] = make_double2(er + wr, ei + wi);
-        if (k) zrow[kb] = make_double2(er - wr, wi - ei);
+        zst(k, make_double2(er + wr, ei + wi));
+        if (k) zst(kb, make_double2(er - wr, wi - ei));
         else *nyq = er - wr;   // X_kH
     }
     if (t == 0) {   // X_{kH/2} = conj Zh[kH/2] (bit-reversed position 1)
         const double2 zm = s.z[hz2k::ix(1)];
-        zrow[kH / 2] = make_double2(zm.x, -zm.y);
+        zst(kH / 2, make_double2(zm.x, -zm.y));
     }
     if (stamps) HZ_DIAG_AT(0, 3);
 }
@@ -191,7 +237,7 @@ __global__ __launch_bounds__(kThreads) void resp_hspec_kernel(const double* __re
                                                              double* __restrict__ Hn) {
     __shared__ hz2k::Lds s;
     const long p0 = (long)blockIdx.x * kP;
-    real_window_fwd(
+    real_window_fwd<kStPlain>(   // setup, once per coefficient change: plain
         s,
         [&](int m) {
             auto g = [&](int k) { return (k < kP && p0 + k < K) ? h[p0 + k] * (1.0 / kF) : 0.0; };
@@ -270,7 +316,7 @@ __global__ __launch_bounds__(kThreads) void resp_fwd_kernel(RespArgs a, hz_modal
     // the pair (m, m + 1), m even, lies in one of hist / x (K and off are even): one 16-byte load
     // when that buffer is 16-byte aligned and the pair is inside the call
     const bool al = ((reinterpret_cast<uintptr_t>(a.hist) | reinterpret_cast<uintptr_t>(a.x)) & 15) == 0;
-    real_window_fwd(
+    real_window_fwd<kStZ>(
         s,
         [&](int mm) {
             const long m = m0 + mm + a.off;
@@ -388,7 +434,7 @@ __global__ __launch_bounds__(256) void resp_mac_kernel_lds(const double2* __rest
     double2(*hs)[kMacBins] = (double2(*)[kMacBins])mac_lds;
     double2(*zs)[kMacBins] = (double2(*)[kMacBins])(mac_lds + QP * kMacBins);
     const int t = threadIdx.x, lq = t & (kMacBins - 1), sl = t >> 6;
-    const int q = (blockIdx.x % (kH / kMacBins)) * kMacBins + lq;
+    const int q0 = (blockIdx.x % (kH / kMacBins)) * kMacBins, q = q0 + lq;
     const int b0 = (blockIdx.x / (kH / kMacBins)) * kMacBlk;
     // Z row of block b, partition p: b + Q - 1 - p = row_lo + (b - b0) + QP - 1 - p; rows < 0 only
     // for p >= Q (zero H rows), read as row 0
@@ -437,10 +483,13 @@ __global__ __launch_bounds__(256) void resp_mac_kernel_lds(const double2* __rest
             zi[0] = z.y;
         }
     }
+    // the workgroup's tile of Y: rows b0 .. min(B, b0 + 32) - 1, bins q0 .. q0 + 63
+    const int nb = min(B - b0, kMacBlk);
+    const Store16<kStY> yst(Y + (long)b0 * kH + q0, (unsigned)sizeof(double2) * ((nb - 1) * kH + kMacBins));
 #pragma unroll
     for (int r = 0; r < BPW; ++r) {
-        const int b = b0 + BPW * sl + r;
-        if (b < B) Y[(long)b * kH + q] = make_double2(ar[r], ai[r]);
+        const int lb = BPW * sl + r;
+        if (lb < nb) yst(lb * kH + lq, make_double2(ar[r], ai[r]));
     }
 }
 
@@ -468,7 +517,7 @@ __global__ __launch_bounds__(256) void resp_mac_kernel_ldsc(const double2* __res
     double2(*hs)[BINS] = (double2(*)[BINS])mac_lds;
     double2(*zs)[BINS] = (double2(*)[BINS])(mac_lds + QP * BINS);
     const int t = threadIdx.x, lq = t & (BINS - 1), sl = t / BINS;
-    const int q = (blockIdx.x % (kH / BINS)) * BINS + lq;
+    const int q0 = (blockIdx.x % (kH / BINS)) * BINS, q = q0 + lq;
     const int b0 = (blockIdx.x / (kH / BINS)) * kMacBlk;
     double2 hv[kHL], zv[kZL];
     auto fetch = [&](int c) {   // chunk c: partitions [24 c, 24 c + 24)
@@ -529,10 +578,12 @@ __global__ __launch_bounds__(256) void resp_mac_kernel_ldsc(const double2* __res
         }
         __syncthreads();   // the next chunk's stores overwrite hs / zs
     }
+    const int nb = min(B - b0, kMacBlk);
+    const Store16<kStY> yst(Y + (long)b0 * kH + q0, (unsigned)sizeof(double2) * ((nb - 1) * kH + BINS));
 #pragma unroll
     for (int r = 0; r < BPW; ++r) {
-        const int b = b0 + BPW * sl + r;
-        if (b < B) Y[(long)b * kH + q] = make_double2(ar[r], ai[r]);
+        const int lb = BPW * sl + r;
+        if (lb < nb) yst(lb * kH + lq, make_double2(ar[r], ai[r]));
     }
 }
 // The long-horizon MAC is latency-bound per chunk (each chunk's operands are fetched one chunk ahead,
@@ -610,21 +661,21 @@ __device__ __forceinline__ void resp_upkeep(const RespArgs& a, long b, const Upk
     // nothing there (disjoint shares)
     if (a.zero_outside)
         for (long i = g; i < a.n - a.n_out; i += stride) a.out[i < a.off ? i : i + a.n_out] = 0.0;
-    if (g < a.K) a.hist_next[g] = u.h;
+    if (g < a.K) store8<kStUpkeep>(a.hist_next + g, u.h);
     for (long i = g + stride; i < a.K; i += stride) {
         const long m = a.n + i;
-        a.hist_next[i] = m < a.K ? a.hist[m] : a.x[m - a.K];
+        store8<kStUpkeep>(a.hist_next + i, m < a.K ? a.hist[m] : a.x[m - a.K]);
     }
     if (g < a.N) {
-        a.pg_next[2 * g] = u.pb + a.sp_n * (u.p0 - u.pb);
-        a.pg_next[2 * g + 1] = u.gb + a.sg_n * (u.g0 - u.gb);
+        store8<kStUpkeep>(a.pg_next + 2 * g, u.pb + a.sp_n * (u.p0 - u.pb));
+        store8<kStUpkeep>(a.pg_next + 2 * g + 1, u.gb + a.sg_n * (u.g0 - u.gb));
     }
     for (long n = g + stride; n < a.N; n += stride) {
         const double P0 = a.pg[2 * n], G0 = a.pg[2 * n + 1], pb = a.pin[n], gb = a.gin[n];
-        a.pg_next[2 * n] = pb + a.sp_n * (P0 - pb);
-        a.pg_next[2 * n + 1] = gb + a.sg_n * (G0 - gb);
+        store8<kStUpkeep>(a.pg_next + 2 * n, pb + a.sp_n * (P0 - pb));
+        store8<kStUpkeep>(a.pg_next + 2 * n + 1, gb + a.sg_n * (G0 - gb));
     }
-    if (g < a.O) a.xhist_next[g] = u.xh;
+    if (g < a.O) store8<kStUpkeep>(a.xhist_next + g, u.xh);
 }
 
 // output block b: the merge of Y_b into Zh' = E' + i O' (E' = Y[k] + conj Y[kH-k],
@@ -717,11 +768,15 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) v
     // z[kH/2 + r], r = t + 256 (i - 4): output samples bP + 2r, bP + 2r + 1 (one 16-byte store
     // when the output is 16-byte aligned)
     const bool oal = (reinterpret_cast<uintptr_t>(a.out + a.off) & 15) == 0;
+    // the block's whole pairs inside the call (b P is even: a 16-byte aligned base when oal)
+    const long left = a.n_out - b * kP;
+    const Store16<kStOut> ost(reinterpret_cast<double2*>(a.out + a.off + b * kP),
+                              (unsigned)sizeof(double2) * (unsigned)(left <= 0 ? 0 : left >= kP ? kP / 2 : left / 2));
 #pragma unroll
     for (int i = kPT / 2; i < kPT; ++i) {
         const long t0 = b * kP + 2 * (t + (long)(i - kPT / 2) * kThreads);
         if (oal && t0 + 1 < a.n_out) {
-            *reinterpret_cast<double2*>(a.out + a.off + t0) = make_double2(vr[i], vi[i]);
+            ost(t + (i - kPT / 2) * kThreads, make_double2(vr[i], vi[i]));
         } else {
             if (t0 < a.n_out) a.out[a.off + t0] = vr[i];
             if (t0 + 1 < a.n_out) a.out[a.off + t0 + 1] = vi[i];

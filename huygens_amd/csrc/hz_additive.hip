@@ -322,15 +322,13 @@ struct PhaseBank {
     std::vector<double> ft;      // [V*OL] target frequency (Hz)
     std::vector<double> c;       // [V*OL] output weight
     std::vector<double> c_first; // weights of the next call's first sample
-    double* d_c0 = nullptr;
+    hz::DevBuf<double> d_c0;
     std::vector<double> amp, act;
     std::vector<char> alive;
     double scale = 1.0;
     // device
-    double *d_rec = nullptr, *d_phi = nullptr, *d_f = nullptr, *d_ft = nullptr, *d_amp = nullptr,
-           *d_act = nullptr, *d_partial = nullptr, *d_out = nullptr;
-    Task* d_tasks = nullptr;
-    size_t partial_cap = 0, out_cap = 0, task_cap = 0;
+    hz::DevBuf<double> d_rec, d_phi, d_f, d_ft, d_amp, d_act, d_partial, d_out;
+    hz::DevBuf<Task> d_tasks;
     std::vector<double> h_rec;
     std::vector<char> dirty;     // per voice: records need rebuilding
     std::vector<Task> tasks;
@@ -348,9 +346,9 @@ struct PhaseBank {
     // (snapshot restored, exactly that many samples re-rendered), so every sample is the one the
     // per-sample sequence produces.
     static constexpr long kLook = 1024, kLookMin = 64;
-    double* la_buf = nullptr;          // pinned [kLook] rendered outputs
+    hz::PinBuf<double> la_buf;         // pinned [kLook] rendered outputs
     long la_n = 0, la_pos = 0;         // rendered / consumed samples of the speculative block
-    double *d_phi_snap = nullptr, *d_f_snap = nullptr;
+    hz::DevBuf<double> d_phi_snap, d_f_snap;
     std::vector<double> amp_snap, c_first_snap;
     std::vector<char> alive_snap;
     long la_blocks = 0, la_rollbacks = 0;
@@ -377,13 +375,13 @@ struct PhaseBank {
             target_groups = prop.multiProcessorCount;
         HZ_TRY_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         own_stream = true;
-        HZ_TRY_HIP(hipMalloc(&d_rec, sizeof(double) * P * PRec::SIZE));
-        HZ_TRY_HIP(hipMalloc(&d_phi, sizeof(double) * P));
-        HZ_TRY_HIP(hipMalloc(&d_f, sizeof(double) * P));
-        HZ_TRY_HIP(hipMalloc(&d_ft, sizeof(double) * P));
-        HZ_TRY_HIP(hipMalloc(&d_amp, sizeof(double) * V));
-        HZ_TRY_HIP(hipMalloc(&d_act, sizeof(double) * V));
-        HZ_TRY_HIP(hipMalloc(&d_c0, sizeof(double) * P));
+        HZ_TRY(d_rec.reserve(P * PRec::SIZE));
+        HZ_TRY(d_phi.reserve(P));
+        HZ_TRY(d_f.reserve(P));
+        HZ_TRY(d_ft.reserve(P));
+        HZ_TRY(d_amp.reserve(V));
+        HZ_TRY(d_act.reserve(V));
+        HZ_TRY(d_c0.reserve(P));
         HZ_TRY_HIP(hipMemset(d_phi, 0, sizeof(double) * P));
         HZ_TRY_HIP(hipMemset(d_f, 0, sizeof(double) * P));
         return HZ_OK;
@@ -392,11 +390,6 @@ struct PhaseBank {
     void release() {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
-        for (void* p : {(void*)d_rec, (void*)d_phi, (void*)d_f, (void*)d_ft, (void*)d_amp, (void*)d_act,
-                        (void*)d_partial, (void*)d_out, (void*)d_tasks, (void*)d_c0, (void*)d_phi_snap,
-                        (void*)d_f_snap})
-            if (p) (void)hipFree(p);
-        if (la_buf) (void)hipHostFree(la_buf);
         for (hipEvent_t e : ev) (void)hipEventDestroy(e);
         if (own_stream && stream) (void)hipStreamDestroy(stream);
     }
@@ -434,12 +427,7 @@ struct PhaseBank {
         HZ_TRY_HIP(hipMemcpyAsync(d_act, act.data(), sizeof(double) * V, hipMemcpyHostToDevice, stream));
         const int ntasks = (int)tasks.size();
         if (ntasks > 0) {
-            if ((size_t)ntasks > task_cap) {
-                if (d_tasks) HZ_TRY_HIP(hipFree(d_tasks));
-                d_tasks = nullptr;
-                HZ_TRY_HIP(hipMalloc(&d_tasks, sizeof(Task) * ntasks));
-                task_cap = ntasks;
-            }
+            HZ_TRY(d_tasks.reserve(ntasks));
             HZ_TRY_HIP(hipMemcpyAsync(d_tasks, tasks.data(), sizeof(Task) * ntasks, hipMemcpyHostToDevice, stream));
         }
         const bool c0_differs = c_first != c;
@@ -474,12 +462,7 @@ struct PhaseBank {
             nseg = (ntiles + seg_tiles - 1) / seg_tiles;
             const long n_pad = ntiles * kTile;
             const size_t need = G > 1 ? (size_t)G * n_pad : 1;
-            if (need > partial_cap) {
-                if (d_partial) HZ_TRY_HIP(hipFree(d_partial));
-                d_partial = nullptr;
-                HZ_TRY_HIP(hipMalloc(&d_partial, sizeof(double) * need));
-                partial_cap = need;
-            }
+            HZ_TRY(d_partial.reserve(need));
             const size_t lds = sizeof(double) * (kWaves * kL * kPad);
             static bool attr = false;
             if (!attr) {
@@ -551,17 +534,8 @@ struct PhaseBank {
         return HZ_OK;
     }
 
-    int ensure_out(long n) {
-        if ((size_t)n <= out_cap) return HZ_OK;
-        if (d_out) HZ_TRY_HIP(hipFree(d_out));
-        d_out = nullptr;
-        HZ_TRY_HIP(hipMalloc(&d_out, sizeof(double) * n));
-        out_cap = n;
-        return HZ_OK;
-    }
-
     int render_scratch(long n) {
-        HZ_TRY(ensure_out(n));
+        HZ_TRY(d_out.reserve(n));
         return render(d_out, n);
     }
 
@@ -569,16 +543,16 @@ struct PhaseBank {
     int look_ahead() {
         const size_t P = (size_t)V * OL;
         if (!la_buf) {
-            HZ_TRY_HIP(hipHostMalloc((void**)&la_buf, sizeof(double) * kLook));
-            HZ_TRY_HIP(hipMalloc(&d_phi_snap, sizeof(double) * P));
-            HZ_TRY_HIP(hipMalloc(&d_f_snap, sizeof(double) * P));
+            HZ_TRY(la_buf.reserve(kLook));
+            HZ_TRY(d_phi_snap.reserve(P));
+            HZ_TRY(d_f_snap.reserve(P));
         }
         HZ_TRY_HIP(hipMemcpyAsync(d_phi_snap, d_phi, sizeof(double) * P, hipMemcpyDeviceToDevice, stream));
         HZ_TRY_HIP(hipMemcpyAsync(d_f_snap, d_f, sizeof(double) * P, hipMemcpyDeviceToDevice, stream));
         amp_snap = amp;
         alive_snap = alive;
         c_first_snap = c_first;
-        HZ_TRY(ensure_out(kLook));
+        HZ_TRY(d_out.reserve(kLook));
         HZ_TRY(render(d_out, kLook));
         HZ_TRY_HIP(hipMemcpyAsync(la_buf, d_out, sizeof(double) * kLook, hipMemcpyDeviceToHost, stream));
         HZ_TRY_HIP(hipStreamSynchronize(stream));
@@ -598,12 +572,7 @@ struct PhaseBank {
             return HZ_OK;
         }
         HZ_TRY(settle());
-        if ((size_t)n > out_cap) {
-            if (d_out) HZ_TRY_HIP(hipFree(d_out));
-            d_out = nullptr;
-            HZ_TRY_HIP(hipMalloc(&d_out, sizeof(double) * n));
-            out_cap = n;
-        }
+        HZ_TRY(d_out.reserve(n));
         HZ_TRY(render(d_out, n));
         HZ_TRY_HIP(hipMemcpyAsync(out, d_out, sizeof(double) * n, hipMemcpyDeviceToHost, stream));
         HZ_TRY_HIP(hipStreamSynchronize(stream));

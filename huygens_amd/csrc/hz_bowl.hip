@@ -437,10 +437,9 @@ void build_brec(double f, double amp, double d, bool is_float, double* rec) {
 struct hz_bowl {
     int M = 0, device = 0, is_float = 0;
     double n0 = 0;  // phase counter (T) at the next call
-    double *d_rec = nullptr, *d_partial = nullptr;
-    void* d_chain = nullptr;   // (float Bowls) [M] float4 {f, d, a, 0} then [M] double decay steps
-    void* d_out = nullptr;
-    size_t partial_cap = 0, out_cap = 0;
+    hz::DevBuf<double> d_rec, d_partial;
+    hz::DevBuf<char> d_chain;   // (float Bowls) [M] float4 {f, d, a, 0} then [M] double decay steps
+    hz::DevBuf<char> d_out;     // doubles or floats (bytes)
     int target_groups = 256;
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -452,7 +451,7 @@ struct hz_bowl {
     // from a speculative block of kLook samples rendered at once; the state is the phase counter
     // alone, so a rollback sets it to the consumed sample (huygens_hip.h, hz_add_fill)
     static constexpr long kLook = 1024, kLookMin = 64;
-    double* la_buf = nullptr;
+    hz::PinBuf<double> la_buf;
     long la_n = 0, la_pos = 0;
     double n0_snap = 0;
 };
@@ -484,12 +483,7 @@ int bowl_launch(hz_bowl* h, void* d_dst, long n, int out_kind) {
     nseg = (ntiles + seg_tiles - 1) / seg_tiles;
     const long n_pad = ntiles * kTile;
     const size_t need = (size_t)G * n_pad;
-    if (need > h->partial_cap) {
-        if (h->d_partial) HZ_TRY_HIP(hipFree(h->d_partial));
-        h->d_partial = nullptr;
-        HZ_TRY_HIP(hipMalloc(&h->d_partial, sizeof(double) * need));
-        h->partial_cap = need;
-    }
+    HZ_TRY(h->d_partial.reserve(need));
     const size_t lds = sizeof(double) * (kWaves * kL * kPad + kWaves * 2 * kMaxPerWave);
     static bool attr = false;
     if (!attr) {
@@ -558,7 +552,7 @@ void bowl_settle(hz_bowl* h) {
 int bowl_host(hz_bowl* h, void* out, size_t elem, long n, int kind);
 
 int bowl_look_ahead(hz_bowl* h) {
-    if (!h->la_buf) HZ_TRY_HIP(hipHostMalloc((void**)&h->la_buf, sizeof(double) * hz_bowl::kLook));
+    HZ_TRY(h->la_buf.reserve(hz_bowl::kLook));
     h->n0_snap = h->n0;
     HZ_TRY(bowl_host(h, h->la_buf, sizeof(double), hz_bowl::kLook, 1));
     h->la_n = hz_bowl::kLook;
@@ -568,12 +562,7 @@ int bowl_look_ahead(hz_bowl* h) {
 
 int bowl_host(hz_bowl* h, void* out, size_t elem, long n, int kind) {
     if (n <= 0) return HZ_OK;
-    if ((size_t)n * elem > h->out_cap) {
-        if (h->d_out) HZ_TRY_HIP(hipFree(h->d_out));
-        h->d_out = nullptr;
-        HZ_TRY_HIP(hipMalloc(&h->d_out, elem * n));
-        h->out_cap = elem * n;
-    }
+    HZ_TRY(h->d_out.reserve(elem * n));
     HZ_TRY(bowl_launch(h, h->d_out, n, kind));
     HZ_TRY_HIP(hipMemcpyAsync(out, h->d_out, elem * n, hipMemcpyDeviceToHost, h->stream));
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
@@ -612,11 +601,10 @@ int hz_bowl_create(int overtones, const double* f, const double* a, const double
         build_brec(fi, ai, di, h->is_float, &rec[(size_t)i * BRec::SIZE]);
     }
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&h->d_rec, sizeof(double) * rec.size()) != hipSuccess ||
+        h->d_rec.reserve(rec.size()) != HZ_OK ||
         hipMemcpy(h->d_rec, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice) != hipSuccess) {
         hz::set_error("hz_bowl_create: device allocation failed");
         if (h->stream) (void)hipStreamDestroy(h->stream);
-        if (h->d_rec) (void)hipFree(h->d_rec);
         delete h;
         return HZ_E_ALLOC;
     }
@@ -632,7 +620,7 @@ int hz_bowl_create(int overtones, const double* f, const double* a, const double
             rs[i] = r[BRec::R];
         }
         const size_t fb = sizeof(float) * fda.size();
-        if (hipMalloc(&h->d_chain, fb + sizeof(double) * rs.size()) != hipSuccess ||
+        if (h->d_chain.reserve(fb + sizeof(double) * rs.size()) != HZ_OK ||
             hipMemcpy(h->d_chain, fda.data(), fb, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy((char*)h->d_chain + fb, rs.data(), sizeof(double) * rs.size(), hipMemcpyHostToDevice) !=
                 hipSuccess) {
@@ -649,9 +637,6 @@ int hz_bowl_destroy(hz_bowl* h) {
     if (!h) return HZ_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void* p : {(void*)h->d_rec, (void*)h->d_partial, h->d_out, h->d_chain})
-        if (p) (void)hipFree(p);
-    if (h->la_buf) (void)hipHostFree(h->la_buf);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -785,7 +770,7 @@ int hz_bowl_fill_delaybank(hz_bowl* h, float* d_buf, hz_dly* bank, void* d_out, 
         HZ_TRY_HIP(hipEventRecord(e[0], h->stream));
     }
     ChainArgs a;
-    a.fda = (const float4*)h->d_chain;
+    a.fda = (const float4*)h->d_chain.get();
     a.rstep = (const double*)((const char*)h->d_chain + sizeof(float4) * h->M);
     a.M = h->M;
     a.n0 = h->n0;

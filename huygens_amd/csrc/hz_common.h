@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "../../include/huygens_hip.h"
+#include "hz_buf.h"
 
 namespace hz {
 

@@ -177,10 +177,9 @@ struct hz_dly {
     long Lc = 0;                    // sub-block length (<= 0: unbounded)
     int split = 0;                  // 0 auto, 1 one workgroup per line, 2 launch per sub-block
     int target_groups = 256;
-    int4* d_taps = nullptr;
-    void *d_gains = nullptr, *d_rx = nullptr, *d_ry = nullptr;
-    void *d_y = nullptr, *d_in = nullptr, *d_out = nullptr;
-    size_t y_cap = 0, in_cap = 0, out_cap = 0;
+    hz::DevBuf<int4> d_taps;
+    hz::DevBuf<char> d_gains, d_rx, d_ry;   // doubles or floats (elem() bytes each)
+    hz::DevBuf<char> d_y, d_in, d_out;
     hipStream_t stream = nullptr;
     bool own_stream = false;
     bool prof = false;
@@ -255,21 +254,12 @@ int dly_upload(hz_dly* h) {
     return HZ_OK;
 }
 
-int ensure(void** p, size_t* cap, size_t bytes) {
-    if (bytes <= *cap) return HZ_OK;
-    if (*p) HZ_TRY_HIP(hipFree(*p));
-    *p = nullptr;
-    HZ_TRY_HIP(hipMalloc(p, bytes));
-    *cap = bytes;
-    return HZ_OK;
-}
-
 template <typename T>
 int dly_launch_t(hz_dly* h, const void* d_in, void* d_out, long n, int in_per_line, int mix) {
     const int N = h->N;
     void* y = d_out;
     if (mix) {
-        HZ_TRY(ensure(&h->d_y, &h->y_cap, sizeof(T) * (size_t)N * n));
+        HZ_TRY(h->d_y.reserve(sizeof(T) * (size_t)N * n));
         y = h->d_y;
     }
     const long Lc = (h->Lc > 0) ? std::min<long>(h->Lc, n) : n;
@@ -377,9 +367,9 @@ int dly_block_begin(hz_dly* h, long n, DlyBlock* b, bool* fusable) {
     HZ_TRY(dly_check(h));
     HZ_TRY(dly_upload(h));
     b->taps = h->d_taps;
-    b->gains = (const float*)h->d_gains;
-    b->rx = (float*)h->d_rx;
-    b->ry = (float*)h->d_ry;
+    b->gains = (const float*)h->d_gains.get();
+    b->rx = (float*)h->d_rx.get();
+    b->ry = (float*)h->d_ry.get();
     b->size = h->size;
     b->o0 = h->origin;
     b->N = h->N;
@@ -433,17 +423,15 @@ int hz_dly_create(int lines, unsigned sparsity, unsigned time, int is_float, int
         h->target_groups = prop.multiProcessorCount;
     const size_t ring = h->elem() * (size_t)lines * h->size;
     bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_taps, sizeof(int4) * (size_t)lines * 2 * sparsity) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_gains, h->elem() * (size_t)lines * 2 * sparsity) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_rx, ring) == hipSuccess && hipMalloc(&h->d_ry, ring) == hipSuccess;
+    ok = ok && h->d_taps.reserve((size_t)lines * 2 * sparsity) == HZ_OK;
+    ok = ok && h->d_gains.reserve(h->elem() * (size_t)lines * 2 * sparsity) == HZ_OK;
+    ok = ok && h->d_rx.reserve(ring) == HZ_OK && h->d_ry.reserve(ring) == HZ_OK;
     ok = ok && hipMemsetAsync(h->d_rx, 0, ring, h->stream) == hipSuccess;   // Buffer: zeroed
     ok = ok && hipMemsetAsync(h->d_ry, 0, ring, h->stream) == hipSuccess;
     ok = ok && hipStreamSynchronize(h->stream) == hipSuccess;
     if (!ok) {
         hz::set_error("hz_dly_create: device allocation failed (%zu bytes of rings)", 2 * ring);
         if (h->stream) (void)hipStreamDestroy(h->stream);
-        for (void* p : {(void*)h->d_taps, h->d_gains, h->d_rx, h->d_ry})
-            if (p) (void)hipFree(p);
         delete h;
         return HZ_E_ALLOC;
     }
@@ -456,8 +444,6 @@ int hz_dly_destroy(hz_dly* h) {
     if (!h) return HZ_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void* p : {(void*)h->d_taps, h->d_gains, h->d_rx, h->d_ry, h->d_y, h->d_in, h->d_out})
-        if (p) (void)hipFree(p);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -505,8 +491,8 @@ int hz_dly_process(hz_dly* h, const void* in, void* out, size_t n, int in_per_li
     if (!in || !out) return HZ_E_INVALID;
     const size_t in_bytes = h->elem() * n * (in_per_line ? h->N : 1);
     const size_t out_bytes = h->elem() * n * (mix ? 1 : h->N);
-    HZ_TRY(ensure(&h->d_in, &h->in_cap, in_bytes));
-    HZ_TRY(ensure(&h->d_out, &h->out_cap, out_bytes));
+    HZ_TRY(h->d_in.reserve(in_bytes));
+    HZ_TRY(h->d_out.reserve(out_bytes));
     HZ_TRY_HIP(hipMemcpyAsync(h->d_in, in, in_bytes, hipMemcpyHostToDevice, h->stream));
     HZ_TRY(dly_launch(h, h->d_in, h->d_out, (long)n, in_per_line, mix));
     HZ_TRY_HIP(hipMemcpyAsync(out, h->d_out, out_bytes, hipMemcpyDeviceToHost, h->stream));

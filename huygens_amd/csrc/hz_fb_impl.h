@@ -1,6 +1,12 @@
-// hz_fb_impl.h -- private header shared by the two Filterbank<double> translation units:
+// hz_fb_impl.h -- private header shared by the Filterbank<double> translation units:
 //   hz_filterbank.hip  general engine (time-varying smoothers, distortion functors) + C ABI
 //   hz_fb_lti.hip      converged ("LTI") engine
+//   hz_fb_gemm.hip     its correction GEMM
+//   hz_fb_tv.hip       coefficient-stream calls
+//   hz_fb_resp.hip     stationary engine (long calls of a converged bank)
+//   hz_fb_state.hip    its band-state pass
+//   hz_fb_stream.hip   streaming calls of a stationary bank
+//   hz_fb_rt.hip       per-sample engine
 #pragma once
 
 #include <algorithm>
@@ -58,8 +64,6 @@ __device__ __forceinline__ double readlane_d(double v, int l) {
 
 }  // namespace hz_fbi
 
-constexpr int kMaxOrderRt = 4;   // (= hz_fbi::kMaxOrder)
-
 // ---------------------------------------------------------------------------
 // handle (the opaque hz_fb of include/huygens_hip.h)
 // ---------------------------------------------------------------------------
@@ -83,10 +87,10 @@ struct hz_fb {
     // geometry
     int waves = 16, bands_per_wave = 1;
     // device buffers
-    double *d_rec = nullptr, *d_pin = nullptr, *d_gin = nullptr;
-    double *d_ystate[2] = {nullptr, nullptr}, *d_pg[2] = {nullptr, nullptr};
+    hz::DevBuf<double> d_rec, d_pin, d_gin;
+    hz::DevBuf<double> d_ystate[2], d_pg[2];
     int scur = 0;  // current state buffer (ping-pong per launch)
-    double* d_xhist[2] = {nullptr, nullptr};
+    hz::DevBuf<double> d_xhist[2];
     int xcur = 0;
     // the reference's rings hold O+1 rows; the row the engine state (O rows) leaves out sits in
     // d_ystate[scur ^ 1][.][O-1] / d_xhist[xcur ^ 1][O-1] after a 1-sample call or a tick
@@ -96,16 +100,14 @@ struct hz_fb {
     // segment (horizon), fine prepass parts per segment
     long plan_nseg = 0, plan_skip_tiles = 0;
     int plan_fine = 0, plan_chunk = 0;
-    double* d_partial = nullptr;
-    size_t partial_cap = 0;  // doubles
-    double* d_seg = nullptr;  // segment start states
-    size_t seg_cap = 0;
+    hz::DevBuf<double> d_partial;
+    hz::DevBuf<double> d_seg;  // segment start states
     int target_groups = 256;  // workgroups wanted per launch (CU count)
-    double *d_in = nullptr, *d_out = nullptr;
-    size_t io_cap = 0;       // doubles
+    hz::DevBuf<double> d_in, d_out;
     // host-buffer calls that take the streaming engine: pinned, device-mapped staging the kernel
-    // reads and writes directly ([kStreamBlock] in, then [kStreamBlock] out)
-    double* pin_io = nullptr;   // + 128 completion flags (long long) after the in/out blocks
+    // reads and writes directly ([kStreamBlock] in, then [kStreamBlock] out, then 128 completion
+    // flags (long long))
+    hz::PinBuf<double> pin_io{hipHostMallocCoherent | hipHostMallocMapped};
     long long pin_seq = 0;
     std::vector<double> h_rec;
     hipStream_t stream = nullptr;
@@ -131,11 +133,9 @@ struct hz_fb {
         bool dirty = true;           // coefficients changed since the records were built
         bool fmix_valid = false;     // Fmix matches the current coefficients, pin and gin
         int rs = 0;                  // record size (doubles)
-        double* d_rec = nullptr;
-        size_t cap = 0;
-        double* d_fmix = nullptr;    // [L][L+O]
-        double* d_kt = nullptr;      // [N O padded to 4][L] homogeneous responses (correction GEMM)
-        size_t kt_cap = 0;
+        hz::DevBuf<double> d_rec;
+        hz::DevBuf<double> d_fmix;   // [L][L+O]
+        hz::DevBuf<double> d_kt;     // [N O padded to 4][L] homogeneous responses (correction GEMM)
         long horizon = -2;           // samples after which ||M^k|| < 2^-64 for every band
                                      // (-1: none within 2^18; -2: not computed yet)
     };
@@ -149,11 +149,10 @@ struct hz_fb {
     // overlapped with the next chunk's mix kernel (double-buffered partial slab)
     hipStream_t stream_red = nullptr;
     std::vector<hipEvent_t> sync_ev;  // ordering events (no timing)
-    double* d_xhist_red = nullptr;    // x history at the call start, for the first chunk's reduce
+    hz::DevBuf<double> d_xhist_red;  // x history at the call start, for the first chunk's reduce
     // a coefficient-stream call leaves its last row staged as the coefficients; the row is
     // copied back asynchronously and turned into F/B only when they are next needed
-    double* tv_row = nullptr;         // pinned host copy of the stream's last row
-    size_t tv_row_cap = 0;            // doubles
+    hz::PinBuf<double> tv_row;        // pinned host copy of the stream's last row
     hipEvent_t tv_ev = nullptr;       // the copy's completion
     bool tv_pending = false;
     int tv_kind = 0;
@@ -181,55 +180,37 @@ struct hz_fb {
         // every rank (hz_fb_arm_time_shard after an all-reduce of hz_fb_stationary_ready), so all
         // ranks switch engines in the same call; cleared by every setter
         bool armed = false;
-        double* d_hist[2] = {nullptr, nullptr};   // [K] last K inputs (ping-pong)
-        size_t hist_cap0 = 0, hist_cap1 = 0;
+        hz::DevBuf<double> d_hist[2];    // [K] last K inputs (ping-pong)
         int hcur = 0;
-        double* d_h = nullptr;           // [K] aggregate impulse response
-        size_t h_cap = 0;
-        double* d_hpart = nullptr;       // [64-band groups][K]
-        size_t hpart_cap = 0;
-        double* d_coef = nullptr;        // F [N][O+1], B [N][O]
-        size_t coef_cap = 0;
-        double* d_H = nullptr;           // [Qp][2048] complex partition spectra, then [Qp] bin 2048
-        size_t H_cap = 0;
-        double* d_Z = nullptr;           // [rows][2048] complex window spectra, then [rows] bin 2048
-        size_t Z_cap = 0;
-        double* d_Y = nullptr;           // [B][2048] complex output spectra
-        size_t Y_cap = 0;
-        double* d_tw = nullptr;          // W_4096^k, k < 2048 (complex)
+        hz::DevBuf<double> d_h;          // [K] aggregate impulse response
+        hz::DevBuf<double> d_hpart;      // [64-band groups][K]
+        hz::DevBuf<double> d_coef;       // F [N][O+1], B [N][O]
+        hz::DevBuf<double> d_H;          // [Qp][2048] complex partition spectra, then [Qp] bin 2048
+        hz::DevBuf<double> d_Z;          // [rows][2048] complex window spectra, then [rows] bin 2048
+        hz::DevBuf<double> d_Y;          // [B][2048] complex output spectra
+        hz::DevBuf<double> d_tw;         // W_4096^k, k < 2048 (complex)
         // column-split path (hz_fb_col.h): W_4096^k for k < 4096, H in column layout, the inverse
         // columns T of a call, the combine's column map
         bool col_on = false;             // hz_fb_tune_response_engine (column split: opt-in)
         int last_engine = 0;             // 0 three-kernel, 1 column-split (last stationary call)
-        double* d_tw4k = nullptr;
-        double* d_Hc = nullptr;
-        size_t Hc_cap = 0;
-        double* d_T = nullptr;
-        size_t T_cap = 0;
-        unsigned char* d_cmap = nullptr;
-        double* d_sop = nullptr;         // band-state pass: pin E operands (fb_state_prepare)
-        size_t sop_cap = 0;
-        double* d_spart = nullptr;       // band-state pass: segment partials, arrival counters
-        size_t spart_cap = 0;
-        unsigned* d_scount = nullptr;
-        size_t scount_cap = 0;
-        double* d_zero = nullptr;        // N O zeros (x history / start of the zero-start pass)
-        size_t zero_cap = 0;
+        hz::DevBuf<double> d_tw4k;
+        hz::DevBuf<double> d_Hc;
+        hz::DevBuf<double> d_T;
+        hz::DevBuf<unsigned char> d_cmap;
+        hz::DevBuf<double> d_sop;        // band-state pass: pin E operands (fb_state_prepare)
+        hz::DevBuf<double> d_spart;      // band-state pass: segment partials, arrival counters
+        hz::DevBuf<unsigned> d_scount;
+        hz::DevBuf<double> d_zero;       // N O zeros (x history / start of the zero-start pass)
         // modal band states (hz_fb_modal.h): banks whose poles sit on one circle on the 2 pi / 8192
         // grid get their states from a fold and one DFT instead of the MFMA pass
         bool modal_on = true;            // hz_fb_tune_modal
         bool modal_ok = false;           // the current bank qualifies (built with d_h)
         bool modal_last = false;         // the last stationary call used it
-        double* d_mpar = nullptr;        // BandPar [N]
-        size_t mpar_cap = 0;
-        double* d_mtab = nullptr;        // R_g^r [8192], R_g^(8192 s) [S], e^(2 pi i q / 8192) [8192]
-        size_t mtab_cap = 0;
-        double* d_mA = nullptr;          // [2][64][128] complex (phase 1 -> phase 2)
-        size_t mA_cap = 0;
-        double* d_mexc = nullptr;        // exceptional responses [nexc][K + 1], then their partials
-        size_t mexc_cap = 0;
-        int* d_mint = nullptr;           // csr_ptr [65], csr (band, k2) [N], exceptional bands [8]
-        size_t mint_cap = 0;
+        hz::DevBuf<double> d_mpar;       // BandPar [N]
+        hz::DevBuf<double> d_mtab;       // R_g^r [8192], R_g^(8192 s) [S], e^(2 pi i q / 8192) [8192]
+        hz::DevBuf<double> d_mA;         // [2][64][128] complex (phase 1 -> phase 2)
+        hz::DevBuf<double> d_mexc;       // exceptional responses [nexc][K + 1], then their partials
+        hz::DevBuf<int> d_mint;          // csr_ptr [65], csr (band, k2) [N], exceptional bands [8]
         int mexc_n = 0, mexc_chunks = 0, mS = 0;
         long h_gen = 0;                  // d_h rebuilds (the streaming spectra follow it)
         // streaming calls (hz_fb_stream.hip): 1024-sample blocks of a stationary bank, one launch
@@ -237,18 +218,16 @@ struct hz_fb {
         struct Stream {
             bool on = true;              // engine enabled (hz_fb_tune_stream)
             long R = 0;                  // ring length (K + 2048); the ring holds 2 R doubles
-            double* d_line = nullptr;    // [2 R]: sample of position i at i mod R and i mod R + R
-            size_t line_cap = 0;
+            hz::DevBuf<double> d_line;   // [2 R]: sample of position i at i mod R and i mod R + R
             long pos = 0;                // samples written; the history is positions [pos - K, pos)
             bool line_hist = false;      // the history lives in the ring (not resp.d_hist)
             bool fdl_valid = false;      // d_ZS holds the spectra of the windows ending at pos
             long hs_gen = -1;            // h_gen the partition spectra were built from
             int head = 0;                // slot of the next call's window
-            double *d_ZS = nullptr, *d_HS = nullptr;   // [K/1024][33][32] complex
-            size_t zs_cap = 0, hs_cap = 0;
-            double* d_CR = nullptr;      // [2][33][32] tail columns C, then [2][33][32] MAC sums R (complex)
+            hz::DevBuf<double> d_ZS, d_HS;   // [K/1024][33][32] complex
+            hz::DevBuf<double> d_CR;     // [2][33][32] tail columns C, then [2][33][32] MAC sums R (complex)
             long blk = 0;                // streamed blocks since the ring was primed (parity of C / R)
-            double* d_tw = nullptr;      // twiddles (W_64, W_32, W_2048)
+            hz::DevBuf<double> d_tw;     // twiddles (W_64, W_32, W_2048)
             long pend = 0;               // streamed samples not yet applied to the smoothers / x history
             long calls = 0;
             long long* flags_dev = nullptr;   // completion flags of a host-buffer call (hz_fb_process)
@@ -259,12 +238,9 @@ struct hz_fb {
             bool tail = false;
             long K1 = 0;                 // head horizon (<= 2^17)
             int tQ = 0;                  // tail partitions of 2048
-            double* d_tH = nullptr;      // [tQp][2048] complex tail partition spectra, then [tQp] bin 2048
-            size_t tH_cap = 0;
-            double *d_tZ = nullptr, *d_tY = nullptr;   // the tail convolution's window / output spectra
-            size_t tZ_cap = 0, tY_cap = 0;
-            double* d_tout = nullptr;    // [2][16384] tail outputs of epochs e (slot e & 1)
-            size_t tout_cap = 0;
+            hz::DevBuf<double> d_tH;     // [tQp][2048] complex tail partition spectra, then [tQp] bin 2048
+            hz::DevBuf<double> d_tZ, d_tY;   // the tail convolution's window / output spectra
+            hz::DevBuf<double> d_tout;   // [2][16384] tail outputs of epochs e (slot e & 1)
             long tail_launched = -1;     // last epoch whose tail convolution was issued
             bool tail_async[2] = {false, false};   // that slot's convolution ran on the side stream
             hipStream_t side = nullptr;
@@ -279,22 +255,19 @@ struct hz_fb {
             double dmax = 0;             // bound on max |D_n| at dref (decay check)
             double gin_max = 0;          // max |gin_n| (the decay check's scale)
             long dsetters = 0;           // setters applied as transients
-            double* d_hD = nullptr;      // [K1] h_D
-            size_t hD_cap = 0;
-            double* d_HSD = nullptr;     // [K1/1024 + 8][33][32] its spectra
-            size_t hsd_cap = 0;
-            double* d_CRD = nullptr;     // its C / R parities
+            hz::DevBuf<double> d_hD;     // [K1] h_D
+            hz::DevBuf<double> d_HSD;    // [K1/1024 + 8][33][32] its spectra
+            hz::DevBuf<double> d_CRD;    // its C / R parities
             // r_n (pre = pin, no gain) in partition form (hz_fb_stream.hip stream_rbasis_kernel)
-            double* d_r0 = nullptr;      // [N][1024] partition 0
-            double* d_phi = nullptr;     // [N][O][1024] homogeneous basis responses
-            double* d_st = nullptr;      // [N][Q][O] states at the partition starts
-            double* d_rsp = nullptr;     // [N][O + 1][33][32] double2: spectra of r0, phi
-            size_t r0_cap = 0, phi_cap = 0, st_cap = 0, rsp_cap = 0;
+            hz::DevBuf<double> d_r0;     // [N][1024] partition 0
+            hz::DevBuf<double> d_phi;    // [N][O][1024] homogeneous basis responses
+            hz::DevBuf<double> d_st;     // [N][Q][O] states at the partition starts
+            hz::DevBuf<double> d_rsp;    // [N][O + 1][33][32] double2: spectra of r0, phi
             bool rband_valid = false;
-            double* d_sgpow = nullptr;   // s_g^j, j < 1024
+            hz::DevBuf<double> d_sgpow;  // s_g^j, j < 1024
             double sgpow_of = -1;        // the s_g it holds
             std::vector<double> h_delta;   // the last setter's bands
-            unsigned long long* d_trace = nullptr;   // (diagnostic, HZ_STREAM_TRACE) launch timelines
+            hz::DevBuf<unsigned long long> d_trace;   // (diagnostic, HZ_STREAM_TRACE) launch timelines
             int trace_n = 0, trace_kind[1024] = {}, trace_wg[1024] = {};
             std::vector<double> gin_base;   // the gins d_h is built with
             bool prime_main = false;     // C / R of the main pass to recompute (h changed, ring valid)
@@ -310,7 +283,7 @@ struct hz_fb {
         long pending_ticks = 0;      // tick() calls since the last served request
         double cached = 0;           // the last served sample
         int cached_dist = 0;
-        double xr[kMaxOrderRt + 1] = {};   // input ring (ring order), host mirror
+        double xr[hz_fbi::kMaxOrder + 1] = {};   // input ring (ring order), host mirror
         long pg_gen = 0, coef_gen = 0;     // generations the server's arrays hold
         // one-band target setters since the server's copy (generation sp_base .. sp_gen): the next
         // sample sends (band, pin, gin) triples instead of both [N] arrays while the list covers
@@ -318,9 +291,8 @@ struct hz_fb {
         std::vector<int> dirty;
         std::vector<unsigned char> mark;   // [N] band in `dirty`
         long sp_base = 0, sp_gen = 0;
-        double* pin1 = nullptr;      // pinned staging (x history, a cached sample)
-        double* d_coef = nullptr;    // [N][2O+1] coefficients, then [N][O+1] ring rows
-        size_t coef_cap = 0;
+        hz::PinBuf<double> pin1;     // pinned staging (x history, a cached sample)
+        hz::DevBuf<double> d_coef;   // [N][2O+1] coefficients, then [N][O+1] ring rows
         std::vector<double> h_coef;
         bool many = false;           // the server last served these rows through OP_FB_MANY
     } rt;
@@ -456,6 +428,5 @@ int fb_rt_stop(hz_fb* h);    // the resident kernel leaves (stream-ordered), pen
 // first (re-mixed with the block's distortion) and ticks; -> samples consumed (0 or 1)
 int fb_rt_resolve(hz_fb* h, double* y0);
 double* fb_rt_cached_slot(hz_fb* h);   // pinned host double for an async copy of that sample
-void fb_rt_free(hz_fb* h);
 
 }  // namespace hz_fbi

@@ -1264,13 +1264,8 @@ int fb_prepare_lti(hz_fb* h, int gi) {
         std::vector<double> host(need, 0.0);
         for (int b = 0; b < h->N; ++b)
             build_record_lti_any(O, L, &h->F[(size_t)b * (O + 1)], &h->B[(size_t)b * O], &host[(size_t)b * rs]);
-        if (need > set.cap) {
-            if (set.d_rec) HZ_TRY_HIP(hipFree(set.d_rec));
-            set.d_rec = nullptr;
-            HZ_TRY_HIP(hipMalloc(&set.d_rec, sizeof(double) * need));
-            set.cap = need;
-        }
-        if (!set.d_fmix) HZ_TRY_HIP(hipMalloc(&set.d_fmix, sizeof(double) * L * (L + kMaxOrder)));
+        HZ_TRY(set.d_rec.reserve(need));
+        HZ_TRY(set.d_fmix.reserve((size_t)L * (L + kMaxOrder)));
         HZ_TRY_HIP(hipMemcpyAsync(set.d_rec, host.data(), sizeof(double) * need, hipMemcpyHostToDevice, h->stream));
         HZ_TRY_HIP(hipStreamSynchronize(h->stream));  // pageable source
         if (fb_lti_gemm_geom(gi) && O > 0) {   // K rows of every band state (+ the Fmix rows, below)
@@ -1281,12 +1276,7 @@ int fb_prepare_lti(hz_fb* h, int gi) {
                 for (int k = 0; k < O; ++k)
                     for (int j = 0; j < L; ++j)
                         kt[((size_t)b * O + k) * L + j] = host[(size_t)b * rs + ko + j * O + k];
-            if (rows * L > set.kt_cap) {
-                if (set.d_kt) HZ_TRY_HIP(hipFree(set.d_kt));
-                set.d_kt = nullptr;
-                HZ_TRY_HIP(hipMalloc(&set.d_kt, sizeof(double) * rows * L));
-                set.kt_cap = rows * L;
-            }
+            HZ_TRY(set.d_kt.reserve(rows * L));
             HZ_TRY_HIP(hipMemcpyAsync(set.d_kt, kt.data(), sizeof(double) * kt.size(), hipMemcpyHostToDevice,
                                       h->stream));
             HZ_TRY_HIP(hipStreamSynchronize(h->stream));
@@ -1345,14 +1335,9 @@ int fb_launch_lti(hz_fb* h, int gi, const double* d_in, double* d_out, long n) {
     const size_t slab = (size_t)G * n_pad_max;
     constexpr int kMaxSlices = 32;   // GEMM band-state slices (rows of part)
     const size_t need = gemm ? (size_t)bs_tot * (n_pad_max / L) + (size_t)kMaxSlices * n_pad_max : 2 * slab;
-    if (need > h->partial_cap) {
-        if (h->d_partial) HZ_TRY_HIP(hipFree(h->d_partial));
-        h->d_partial = nullptr;
-        HZ_TRY_HIP(hipMalloc(&h->d_partial, sizeof(double) * need));
-        h->partial_cap = need;
-    }
+    HZ_TRY(h->d_partial.reserve(need));
     if (!h->stream_red) HZ_TRY_HIP(hipStreamCreateWithFlags(&h->stream_red, hipStreamNonBlocking));
-    if (!h->d_xhist_red) HZ_TRY_HIP(hipMalloc(&h->d_xhist_red, sizeof(double) * kMaxOrder));
+    HZ_TRY(h->d_xhist_red.reserve(kMaxOrder));
     const long nchunks = (n + chunk - 1) / chunk;
     if ((size_t)(2 * nchunks) > h->sync_ev.size()) {
         while (h->sync_ev.size() < (size_t)(2 * nchunks)) {
@@ -1433,13 +1418,8 @@ int fb_launch_lti(hz_fb* h, int gi, const double* d_in, double* d_out, long n) {
         h->plan_chunk = L;
         if (nseg > 1) {
             const size_t sneed = (size_t)h->N * nseg_state * O;
-            if (sneed > h->seg_cap) {
-                HZ_TRY_HIP(hipStreamSynchronize(h->stream));
-                if (h->d_seg) HZ_TRY_HIP(hipFree(h->d_seg));
-                h->d_seg = nullptr;
-                HZ_TRY_HIP(hipMalloc(&h->d_seg, sizeof(double) * sneed));
-                h->seg_cap = sneed;
-            }
+            if (sneed > h->d_seg.cap()) HZ_TRY_HIP(hipStreamSynchronize(h->stream));
+            HZ_TRY(h->d_seg.reserve(sneed));
         }
         double* slab_k = h->d_partial + (size_t)(k & 1) * slab;
         const long nc_pad = ntiles * 64;   // chunks of the launch (GEMM path)

@@ -844,15 +844,6 @@ RespHKernel pick_h(int O) {
     }
 }
 
-int resp_alloc(double** p, size_t* cap, size_t need) {
-    if (need <= *cap) return HZ_OK;
-    if (*p) HZ_TRY_HIP(hipFree(*p));
-    *p = nullptr;
-    HZ_TRY_HIP(hipMalloc(p, need * sizeof(double)));
-    *cap = need;
-    return HZ_OK;
-}
-
 // partitions padded with zero spectra: to the MAC's register window (8), or to whole chunks of the
 // chunked LDS MAC (24) past 24
 int q_padded(int Q) { return Q > 24 ? (Q + 23) / 24 * 24 : (Q + kMacR - 1) / kMacR * kMacR; }
@@ -879,12 +870,12 @@ int resp_setup(hz_fb* h) {
     }
     if (R.K <= 0) return HZ_OK;
     const size_t nz = std::max<size_t>((size_t)h->N * h->order, hz_fbi::kMaxOrder);
-    if (nz > R.zero_cap) {
-        HZ_TRY(resp_alloc(&R.d_zero, &R.zero_cap, nz));
+    if (nz > R.d_zero.cap()) {
+        HZ_TRY(R.d_zero.reserve(nz));
         HZ_TRY_HIP(hipMemset(R.d_zero, 0, sizeof(double) * nz));
     }
-    HZ_TRY(resp_alloc(&R.d_hist[0], &R.hist_cap0, (size_t)R.K));
-    HZ_TRY(resp_alloc(&R.d_hist[1], &R.hist_cap1, (size_t)R.K));
+    HZ_TRY(R.d_hist[0].reserve((size_t)R.K));
+    HZ_TRY(R.d_hist[1].reserve((size_t)R.K));
     if (!R.d_tw4k) {   // column path: W_4096^k, k < 4096, in long double; the combine's column map
         std::vector<double2> tw(kF);
         const long double pi = acosl(-1.0L);
@@ -892,11 +883,11 @@ int resp_setup(hz_fb* h) {
             const long double ang = -2.0L * pi * k / kF;
             tw[k] = make_double2((double)cosl(ang), (double)sinl(ang));
         }
-        HZ_TRY_HIP(hipMalloc((void**)&R.d_tw4k, sizeof(double2) * kF));
+        HZ_TRY(R.d_tw4k.reserve(2 * (size_t)kF));
         HZ_TRY_HIP(hipMemcpy(R.d_tw4k, tw.data(), sizeof(double2) * kF, hipMemcpyHostToDevice));
         unsigned char cm[64];
         hz_col::col_map(cm);
-        HZ_TRY_HIP(hipMalloc((void**)&R.d_cmap, sizeof(cm)));
+        HZ_TRY(R.d_cmap.reserve(sizeof(cm)));
         HZ_TRY_HIP(hipMemcpy(R.d_cmap, cm, sizeof(cm), hipMemcpyHostToDevice));
     }
     if (!R.d_tw) {   // W_F^k, k < kH, in long double
@@ -906,7 +897,7 @@ int resp_setup(hz_fb* h) {
             const long double ang = -2.0L * pi * k / kF;
             tw[k] = make_double2((double)cosl(ang), (double)sinl(ang));
         }
-        HZ_TRY_HIP(hipMalloc((void**)&R.d_tw, sizeof(double2) * tw.size()));
+        HZ_TRY(R.d_tw.reserve(2 * tw.size()));
         HZ_TRY_HIP(hipMemcpy(R.d_tw, tw.data(), sizeof(double2) * tw.size(), hipMemcpyHostToDevice));
     }
     return HZ_OK;
@@ -922,13 +913,13 @@ int resp_build_h(hz_fb* h) {
     const long K = R.K;
     const int G = (N + 63) / 64;
     const int Q = (int)(K / kP), Qp = q_padded(Q);   // zero spectra past Q (the MAC's unguarded blocks)
-    HZ_TRY(resp_alloc(&R.d_coef, &R.coef_cap, (size_t)N * (2 * O + 1)));
+    HZ_TRY(R.d_coef.reserve((size_t)N * (2 * O + 1)));
     HZ_TRY_HIP(hipMemcpyAsync(R.d_coef, h->F.data(), sizeof(double) * N * (O + 1), hipMemcpyHostToDevice, h->stream));
     HZ_TRY_HIP(hipMemcpyAsync(R.d_coef + (size_t)N * (O + 1), h->B.data(), sizeof(double) * N * O,
                               hipMemcpyHostToDevice, h->stream));
-    HZ_TRY(resp_alloc(&R.d_hpart, &R.hpart_cap, (size_t)G * K));
-    HZ_TRY(resp_alloc(&R.d_h, &R.h_cap, (size_t)K));
-    HZ_TRY(resp_alloc(&R.d_H, &R.H_cap, (size_t)Qp * (2 * kH + 1)));   // [Qp][kH] complex, then [Qp] bin kH
+    HZ_TRY(R.d_hpart.reserve((size_t)G * K));
+    HZ_TRY(R.d_h.reserve((size_t)K));
+    HZ_TRY(R.d_H.reserve((size_t)Qp * (2 * kH + 1)));   // [Qp][kH] complex, then [Qp] bin kH
     HZ_TRY_HIP(hipMemsetAsync(R.d_H, 0, sizeof(double) * (size_t)Qp * (2 * kH + 1), h->stream));
     hipLaunchKernelGGL(pick_h(O), dim3(G), dim3(64), 0, h->stream, (const double*)R.d_coef,
                        (const double*)(R.d_coef + (size_t)N * (O + 1)), (const double*)h->d_pin,
@@ -940,12 +931,12 @@ int resp_build_h(hz_fb* h) {
     if (R.over_valid)   // the whole bank's response (time-range shards)
         HZ_TRY_HIP(hipMemcpyAsync(R.d_h, R.h_over.data(), sizeof(double) * K, hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(resp_hspec_kernel, dim3((unsigned)Q), dim3(kThreads), 0, h->stream, (const double*)R.d_h, K,
-                       (const double2*)R.d_tw, (double2*)R.d_H, R.d_H + (size_t)Qp * 2 * kH);
+                       (const double2*)R.d_tw.get(), (double2*)R.d_H.get(), R.d_H + (size_t)Qp * 2 * kH);
     HZ_TRY_HIP(hipGetLastError());
     if (col_q_ok(Q)) {   // the column path's partition spectra, lane order
-        HZ_TRY(resp_alloc(&R.d_Hc, &R.Hc_cap, (size_t)hz_col::kSlots * Q * 64 * 2));
+        HZ_TRY(R.d_Hc.reserve((size_t)hz_col::kSlots * Q * 64 * 2));
         hipLaunchKernelGGL(hz_col::resp_hcol_kernel, dim3(hz_col::kSlots, (unsigned)Q), dim3(64), 0, h->stream,
-                           (const double2*)R.d_H, (const double*)(R.d_H + (size_t)Qp * 2 * kH), Q, (double2*)R.d_Hc);
+                           (const double2*)R.d_H.get(), (const double*)(R.d_H + (size_t)Qp * 2 * kH), Q, (double2*)R.d_Hc.get());
         HZ_TRY_HIP(hipGetLastError());
     }
     HZ_TRY(hz_fbi::fb_state_prepare(h));   // the state pass's records and operands, for LAZY too
@@ -1053,16 +1044,11 @@ int modal_prepare(hz_fb* h) {
             er[e * (size_t)(K + 1) + t] = (double)y;
         }
     }
-    HZ_TRY(resp_alloc(&R.d_mpar, &R.mpar_cap, (size_t)N * sizeof(BandPar) / sizeof(double)));
-    HZ_TRY(resp_alloc(&R.d_mtab, &R.mtab_cap, tab.size()));
-    HZ_TRY(resp_alloc(&R.d_mA, &R.mA_cap, 2 * 2 * (size_t)kR2 * kR1));
-    HZ_TRY(resp_alloc(&R.d_mexc, &R.mexc_cap, er.size() + exc.size() * (size_t)chunks * 4 + 1));
-    if (ints.size() > R.mint_cap) {
-        if (R.d_mint) HZ_TRY_HIP(hipFree(R.d_mint));
-        R.d_mint = nullptr;
-        HZ_TRY_HIP(hipMalloc(&R.d_mint, sizeof(int) * ints.size()));
-        R.mint_cap = ints.size();
-    }
+    HZ_TRY(R.d_mpar.reserve((size_t)N * sizeof(BandPar) / sizeof(double)));
+    HZ_TRY(R.d_mtab.reserve(tab.size()));
+    HZ_TRY(R.d_mA.reserve(2 * 2 * (size_t)kR2 * kR1));
+    HZ_TRY(R.d_mexc.reserve(er.size() + exc.size() * (size_t)chunks * 4 + 1));
+    HZ_TRY(R.d_mint.reserve(ints.size()));
     HZ_TRY_HIP(hipMemcpyAsync(R.d_mpar, par.data(), sizeof(BandPar) * N, hipMemcpyHostToDevice, h->stream));
     HZ_TRY_HIP(hipMemcpyAsync(R.d_mtab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, h->stream));
     if (!er.empty())
@@ -1097,8 +1083,8 @@ void modal_args(hz_fb* h, const double* hist, const double* x, long n, double* o
     a->wR = R.d_mtab;
     a->RL = R.d_mtab + kL;
     a->tw = (const double2*)(R.d_mtab + kL + R.mS);
-    a->A = (double2*)R.d_mA;
-    a->par = (const BandPar*)R.d_mpar;
+    a->A = (double2*)R.d_mA.get();
+    a->par = (const BandPar*)R.d_mpar.get();
     a->csr_ptr = R.d_mint;
     a->csr = (const int2*)(R.d_mint + kPhase2 + 1);
     a->nexc = R.mexc_n;
@@ -1231,13 +1217,13 @@ int fb_launch_resp(hz_fb* h, const double* d_in, double* d_out, long n) {
     // rows the MAC may read: its last register window (B padded to kMacR output blocks, Qp
     // partitions); rows past nz are never stored, only multiplied into discarded outputs
     const int zrows = (B + 64 - 1) / 64 * 64 + Qp;
-    if ((size_t)zrows * (2 * kH + 1) > R.Z_cap) {
-        HZ_TRY(resp_alloc(&R.d_Z, &R.Z_cap, (size_t)zrows * (2 * kH + 1)));
-        HZ_TRY_HIP(hipMemsetAsync(R.d_Z, 0, sizeof(double) * R.Z_cap, h->stream));
+    if ((size_t)zrows * (2 * kH + 1) > R.d_Z.cap()) {
+        HZ_TRY(R.d_Z.reserve((size_t)zrows * (2 * kH + 1)));
+        HZ_TRY_HIP(hipMemsetAsync(R.d_Z, 0, sizeof(double) * R.d_Z.cap(), h->stream));
     }
     const size_t zn_at = (size_t)zrows * 2 * kH;   // [zrows] bin kH after the rows
     const int ys = Qp > kMacChunk ? macc_splits(Qp) : 1;   // (launch_mac_lds's planes)
-    HZ_TRY(resp_alloc(&R.d_Y, &R.Y_cap, (size_t)ys * B * kH * 2));
+    HZ_TRY(R.d_Y.reserve((size_t)ys * B * kH * 2));
     hipEvent_t* e = nullptr;
     if (h->prof) {
         HZ_TRY(fb_prof_events(h, &e));
@@ -1253,10 +1239,10 @@ int fb_launch_resp(hz_fb* h, const double* d_in, double* d_out, long n) {
     a.n_out = n_out;
     a.Q = Q;
     a.B = B;
-    a.tw = (const double2*)R.d_tw;
-    a.Z = (double2*)R.d_Z;
+    a.tw = (const double2*)R.d_tw.get();
+    a.Z = (double2*)R.d_Z.get();
     a.Zn = R.d_Z + zn_at;
-    a.Y = (const double2*)R.d_Y;
+    a.Y = (const double2*)R.d_Y.get();
     a.ys = ys;
     a.ystride = (long)B * kH;
     a.Hn = R.d_H + (size_t)Qp * 2 * kH;
@@ -1303,7 +1289,7 @@ int fb_launch_resp(hz_fb* h, const double* d_in, double* d_out, long n) {
         // column-split path (hz_fb_col.h): window spectra never leave the column kernel; the
         // combine kernel carries the band-state pass
         const int NR = (B + hz_col::kWB - 1) / hz_col::kWB;
-        HZ_TRY(resp_alloc(&R.d_T, &R.T_cap, (size_t)B * hz_col::kSlots * 64 * 2));
+        HZ_TRY(R.d_T.reserve((size_t)B * hz_col::kSlots * 64 * 2));
         hz_col::ColArgs ca;
         ca.hist = a.hist;
         ca.x = a.x;
@@ -1313,9 +1299,9 @@ int fb_launch_resp(hz_fb* h, const double* d_in, double* d_out, long n) {
         ca.Q = Q;
         ca.B = B;
         ca.NR = NR;
-        ca.tw4k = (const double2*)R.d_tw4k;
-        ca.Hc = (const double2*)R.d_Hc;
-        ca.T = (double2*)R.d_T;
+        ca.tw4k = (const double2*)R.d_tw4k.get();
+        ca.Hc = (const double2*)R.d_Hc.get();
+        ca.T = (double2*)R.d_T.get();
         hipLaunchKernelGGL(pick_col(Q), dim3((unsigned)(hz_col::kUnits * NR)), dim3(hz_col::kColThreads), 0, h->stream, ca);
         HZ_TRY_HIP(hipGetLastError());
         if (e && inside) {
@@ -1324,7 +1310,7 @@ int fb_launch_resp(hz_fb* h, const double* d_in, double* d_out, long n) {
         }
         auto kc = so == 1 ? resp_comb_kernel<1> : so == 2 ? resp_comb_kernel<2> : resp_comb_kernel<0>;
         hipLaunchKernelGGL(kc, dim3((unsigned)(B + (chained ? st.G * st.nseg : 0))), dim3(kThreads), 0, h->stream, a,
-                           (const double2*)R.d_T, (const unsigned char*)R.d_cmap, (const double2*)R.d_tw4k, st);
+                           (const double2*)R.d_T.get(), (const unsigned char*)R.d_cmap, (const double2*)R.d_tw4k.get(), st);
         HZ_TRY_HIP(hipGetLastError());
     } else {
         // profiling with hz_fb_profile(h, rep > 1): each (idempotent) kernel of the modal path launched rep
@@ -1339,7 +1325,7 @@ int fb_launch_resp(hz_fb* h, const double* d_in, double* d_out, long n) {
             h->ev_skip[(e - h->ev.data()) / 5] &= (unsigned char)~2;
         }
         for (int r = 0; r < rep; ++r)
-            launch_mac_lds(Qp, B, (const double2*)R.d_H, (const double2*)R.d_Z, (double2*)R.d_Y, Q, h->stream);
+            launch_mac_lds(Qp, B, (const double2*)R.d_H.get(), (const double2*)R.d_Z.get(), (double2*)R.d_Y.get(), Q, h->stream);
         HZ_TRY_HIP(hipGetLastError());
         if (e && inside) {
             HZ_TRY_HIP(hipEventRecord(e[2], h->stream));
@@ -1451,10 +1437,10 @@ int fb_resp_tail_spectra(hz_fb* h, long K1) {
     hz_fb::Resp::Stream& S = R.st;
     const long Kt = R.K - K1;
     const int Q = (int)(Kt / kP), Qp = q_padded(Q);
-    HZ_TRY(resp_alloc(&S.d_tH, &S.tH_cap, (size_t)Qp * (2 * kH + 1)));
+    HZ_TRY(S.d_tH.reserve((size_t)Qp * (2 * kH + 1)));
     HZ_TRY_HIP(hipMemsetAsync(S.d_tH, 0, sizeof(double) * (size_t)Qp * (2 * kH + 1), h->stream));
     hipLaunchKernelGGL(resp_hspec_kernel, dim3((unsigned)Q), dim3(kThreads), 0, h->stream, (const double*)(R.d_h + K1),
-                       Kt, (const double2*)R.d_tw, (double2*)S.d_tH, S.d_tH + (size_t)Qp * 2 * kH);
+                       Kt, (const double2*)R.d_tw.get(), (double2*)S.d_tH.get(), S.d_tH + (size_t)Qp * 2 * kH);
     HZ_TRY_HIP(hipGetLastError());
     S.tQ = Q;
     return HZ_OK;
@@ -1467,11 +1453,11 @@ int fb_resp_tail_conv(hz_fb* h, const double* u, long n, double* out, hipStream_
     const long Kt = (long)Q * kP;
     const int B = (int)((n + kP - 1) / kP), nz = Q + B - 1;
     const int zrows = (B + 64 - 1) / 64 * 64 + Qp;
-    if ((size_t)zrows * (2 * kH + 1) > S.tZ_cap) {
-        HZ_TRY(resp_alloc(&S.d_tZ, &S.tZ_cap, (size_t)zrows * (2 * kH + 1)));
-        HZ_TRY_HIP(hipMemsetAsync(S.d_tZ, 0, sizeof(double) * S.tZ_cap, st));
+    if ((size_t)zrows * (2 * kH + 1) > S.d_tZ.cap()) {
+        HZ_TRY(S.d_tZ.reserve((size_t)zrows * (2 * kH + 1)));
+        HZ_TRY_HIP(hipMemsetAsync(S.d_tZ, 0, sizeof(double) * S.d_tZ.cap(), st));
     }
-    HZ_TRY(resp_alloc(&S.d_tY, &S.tY_cap, (size_t)B * kH * 2));
+    HZ_TRY(S.d_tY.reserve((size_t)B * kH * 2));
     RespArgs a{};
     a.hist = u;
     a.x = u + Kt;
@@ -1482,10 +1468,10 @@ int fb_resp_tail_conv(hz_fb* h, const double* u, long n, double* out, hipStream_
     a.Q = Q;
     a.B = B;
     a.nz = nz;
-    a.tw = (const double2*)R.d_tw;
-    a.Z = (double2*)S.d_tZ;
+    a.tw = (const double2*)R.d_tw.get();
+    a.Z = (double2*)S.d_tZ.get();
     a.Zn = S.d_tZ + (size_t)zrows * 2 * kH;
-    a.Y = (const double2*)S.d_tY;
+    a.Y = (const double2*)S.d_tY.get();
     a.ys = 1;
     a.Hn = S.d_tH + (size_t)Qp * 2 * kH;
     a.out = out;
@@ -1494,8 +1480,8 @@ int fb_resp_tail_conv(hz_fb* h, const double* u, long n, double* out, hipStream_
     hipLaunchKernelGGL(resp_fwd_kernel, dim3((unsigned)nz), dim3(kThreads), 0, st, a, hz_modal::ModalArgs());
     HZ_TRY_HIP(hipGetLastError());
     const int nmac = (kH / 256) * ((B + kMacR - 1) / kMacR);
-    hipLaunchKernelGGL(pick_mac(Qp), dim3((unsigned)nmac), dim3(256), 0, st, (const double2*)S.d_tH,
-                       (const double2*)S.d_tZ, (double2*)S.d_tY, Q, Qp, B);
+    hipLaunchKernelGGL(pick_mac(Qp), dim3((unsigned)nmac), dim3(256), 0, st, (const double2*)S.d_tH.get(),
+                       (const double2*)S.d_tZ.get(), (double2*)S.d_tY.get(), Q, Qp, B);
     HZ_TRY_HIP(hipGetLastError());
     hipLaunchKernelGGL(resp_inv_kernel<0>, dim3((unsigned)B), dim3(kThreads), 0, st, a, hz_state::StateArgs(),
                        hz_modal::ModalArgs());
@@ -1505,15 +1491,9 @@ int fb_resp_tail_conv(hz_fb* h, const double* u, long n, double* out, hipStream_
 
 void fb_resp_free(hz_fb* h) {
     hz_fb::Resp& R = h->resp;
-    for (double* p : {R.d_hist[0], R.d_hist[1], R.d_h, R.d_hpart, R.d_coef, R.d_zero, R.d_H, R.d_Z, R.d_Y, R.d_tw,
-                      R.d_spart, R.d_sop, R.d_tw4k, R.d_Hc, R.d_T, R.d_mpar, R.d_mtab, R.d_mA, R.d_mexc})
-        if (p) (void)hipFree(p);
-    if (R.d_cmap) (void)hipFree(R.d_cmap);
-    if (R.d_scount) (void)hipFree(R.d_scount);
-    if (R.d_mint) (void)hipFree(R.d_mint);
     fb_stream_free(h);
     const bool col_on = R.col_on, modal_on = R.modal_on;
-    R = hz_fb::Resp();
+    R = hz_fb::Resp();   // (frees the buffers)
     R.col_on = col_on;
     R.modal_on = modal_on;
 }

@@ -91,14 +91,9 @@ static int rt_enter(hz_fb* h) {
     HZ_TRY(fb_upload_staged(h));
     HZ_TRY(fb_resp_materialize(h));
     const size_t nc = (size_t)N * (2 * O + 1), nr = (size_t)N * (O + 1);
-    if (nc + nr > T.coef_cap) {
-        HZ_TRY_HIP(hipStreamSynchronize(h->stream));
-        if (T.d_coef) HZ_TRY_HIP(hipFree(T.d_coef));
-        T.d_coef = nullptr;
-        HZ_TRY_HIP(hipMalloc(&T.d_coef, sizeof(double) * (nc + nr)));
-        T.coef_cap = nc + nr;
-    }
-    if (!T.pin1) HZ_TRY_HIP(hipHostMalloc((void**)&T.pin1, sizeof(double) * 16));
+    if (nc + nr > T.d_coef.cap()) HZ_TRY_HIP(hipStreamSynchronize(h->stream));
+    HZ_TRY(T.d_coef.reserve(nc + nr));
+    HZ_TRY(T.pin1.reserve(16));
     T.h_coef.resize(nc);
     for (int n = 0; n < N; ++n) {
         for (int i = 0; i <= O; ++i) T.h_coef[(size_t)n * (2 * O + 1) + i] = h->F[(size_t)n * (O + 1) + i];
@@ -174,15 +169,6 @@ int fb_rt_resolve(hz_fb* h, double* y0) {
 }
 
 double* fb_rt_cached_slot(hz_fb* h) { return h->rt.pin1 + 15; }
-
-void fb_rt_free(hz_fb* h) {
-    hz_fb::Rt& T = h->rt;
-    if (T.pin1) (void)hipHostFree(T.pin1);
-    if (T.d_coef) (void)hipFree(T.d_coef);
-    T.pin1 = nullptr;
-    T.d_coef = nullptr;
-    T.active = false;
-}
 
 // operator() with the handle held (the entry point below, or a block call resolving a cached sample)
 static int sample_locked(hz_fb* h, double x, int dist_id, double param, double* y) {

@@ -102,13 +102,8 @@ int fb_state_prepare(hz_fb* h) {
     hz_fb::Resp& R = h->resp;
     const int G = (h->N + bands_per_group(O) - 1) / bands_per_group(O);
     const size_t need = (size_t)G * grp_doubles(O);
-    if (need > R.sop_cap) {
-        HZ_TRY_HIP(hipDeviceSynchronize());
-        if (R.d_sop) HZ_TRY_HIP(hipFree(R.d_sop));
-        R.d_sop = nullptr;
-        HZ_TRY_HIP(hipMalloc(&R.d_sop, sizeof(double) * need));
-        R.sop_cap = need;
-    }
+    if (need > R.d_sop.cap()) HZ_TRY_HIP(hipDeviceSynchronize());
+    HZ_TRY(R.d_sop.reserve(need));
     hipLaunchKernelGGL(pick_state_ops(O), dim3((unsigned)((need + 255) / 256)), dim3(256), 0, h->stream,
                        (const double*)set.d_rec, set.rs, (const double*)h->d_pin, h->N, G, R.d_sop);
     HZ_TRY_HIP(hipGetLastError());
@@ -132,20 +127,12 @@ static int state_args(hz_fb* h, const double* x, long len, double* out, StateArg
     hz_fb::Resp& R = h->resp;
     if (nseg > 1) {
         const size_t need = (size_t)G * nseg * kCols;
-        if (need > R.spart_cap) {
+        if (need > R.d_spart.cap()) HZ_TRY_HIP(hipDeviceSynchronize());
+        HZ_TRY(R.d_spart.reserve(need));
+        if ((size_t)G > R.d_scount.cap()) {   // new arrival counters start at zero
             HZ_TRY_HIP(hipDeviceSynchronize());
-            if (R.d_spart) HZ_TRY_HIP(hipFree(R.d_spart));
-            R.d_spart = nullptr;
-            HZ_TRY_HIP(hipMalloc(&R.d_spart, sizeof(double) * need));
-            R.spart_cap = need;
-        }
-        if ((size_t)G > R.scount_cap) {
-            HZ_TRY_HIP(hipDeviceSynchronize());
-            if (R.d_scount) HZ_TRY_HIP(hipFree(R.d_scount));
-            R.d_scount = nullptr;
-            HZ_TRY_HIP(hipMalloc(&R.d_scount, sizeof(unsigned) * G));
+            HZ_TRY(R.d_scount.reserve(G));
             HZ_TRY_HIP(hipMemset(R.d_scount, 0, sizeof(unsigned) * G));
-            R.scount_cap = G;
         }
     }
     *a = StateArgs();

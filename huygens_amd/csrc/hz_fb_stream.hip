@@ -987,15 +987,6 @@ __global__ __launch_bounds__(256) void stream_upkeep_kernel(double* __restrict__
     if (b < O) xhist[b] = line[last - b];   // last = ring index + R of the newest sample
 }
 
-int s_alloc(double** p, size_t* cap, size_t need) {
-    if (need <= *cap) return HZ_OK;
-    if (*p) HZ_TRY_HIP(hipFree(*p));
-    *p = nullptr;
-    HZ_TRY_HIP(hipMalloc(p, need * sizeof(double)));
-    *cap = need;
-    return HZ_OK;
-}
-
 // the side stream's work on the ring done (before anything else reuses or rewrites it)
 int tail_quiet(hz_fb::Resp::Stream& S) {
     if (S.side) HZ_TRY_HIP(hipStreamSynchronize(S.side));
@@ -1023,13 +1014,13 @@ int stream_setup(hz_fb* h) {
     }
     S.tail = tail;
     S.K1 = K1;
-    const size_t lcap = S.line_cap;
-    HZ_TRY(s_alloc(&S.d_line, &S.line_cap, (size_t)(2 * ring)));
+    const size_t lcap = S.d_line.cap();
+    HZ_TRY(S.d_line.reserve((size_t)(2 * ring)));
     // never-written positions are zeros: a tail convolution's windows reach back past the history
     // (into outputs nobody reads), and a stale NaN there would spread through the window's FFT
-    if (S.line_cap != lcap) HZ_TRY_HIP(hipMemset(S.d_line, 0, sizeof(double) * S.line_cap));
+    if (S.d_line.cap() != lcap) HZ_TRY_HIP(hipMemset(S.d_line, 0, sizeof(double) * S.d_line.cap()));
     if (tail) {
-        HZ_TRY(s_alloc(&S.d_tout, &S.tout_cap, (size_t)(2 * kE)));
+        HZ_TRY(S.d_tout.reserve((size_t)(2 * kE)));
         if (!S.side) {
             HZ_TRY_HIP(hipStreamCreateWithFlags(&S.side, hipStreamNonBlocking));
             HZ_TRY_HIP(hipEventCreateWithFlags(&S.ev_main, hipEventDisableTiming));
@@ -1038,14 +1029,14 @@ int stream_setup(hz_fb* h) {
         }
     }
     const size_t col = (size_t)kCols * 32 * 2;   // doubles per spectrum (33 columns x 32 bins)
-    const size_t zcap = S.zs_cap, hcap = S.hs_cap;
-    HZ_TRY(s_alloc(&S.d_ZS, &S.zs_cap, (size_t)(K1 / kSP) * col));
-    HZ_TRY(s_alloc(&S.d_HS, &S.hs_cap, (size_t)(K1 / kSP + 8) * col));   // 8 zero rows past Q
+    const size_t zcap = S.d_ZS.cap(), hcap = S.d_HS.cap();
+    HZ_TRY(S.d_ZS.reserve((size_t)(K1 / kSP) * col));
+    HZ_TRY(S.d_HS.reserve((size_t)(K1 / kSP + 8) * col));   // 8 zero rows past Q
     // zero rows (and never-written slots) must be exact zeros: the MAC multiplies them
-    if (S.zs_cap != zcap) HZ_TRY_HIP(hipMemset(S.d_ZS, 0, sizeof(double) * S.zs_cap));
-    if (S.hs_cap != hcap) HZ_TRY_HIP(hipMemset(S.d_HS, 0, sizeof(double) * S.hs_cap));
+    if (S.d_ZS.cap() != zcap) HZ_TRY_HIP(hipMemset(S.d_ZS, 0, sizeof(double) * S.d_ZS.cap()));
+    if (S.d_HS.cap() != hcap) HZ_TRY_HIP(hipMemset(S.d_HS, 0, sizeof(double) * S.d_HS.cap()));
     if (!S.d_CR) {   // tail columns C and MAC sums R, two parities each
-        HZ_TRY_HIP(hipMalloc(&S.d_CR, sizeof(double) * 4 * col));
+        HZ_TRY(S.d_CR.reserve(4 * col));
         HZ_TRY_HIP(hipMemset(S.d_CR, 0, sizeof(double) * 4 * col));
     }
     if (!S.d_tw) {   // in long double
@@ -1058,7 +1049,7 @@ int stream_setup(hz_fb* h) {
         for (int m = 0; m < 64; ++m) tw[kTw64 + m] = root(m, 64);
         for (int m = 0; m < 32; ++m) tw[kTw32 + m] = root(m, 32);
         for (int m = 0; m < 1024; ++m) tw[kTw2k + m] = root(m, kSF);
-        HZ_TRY_HIP(hipMalloc(&S.d_tw, sizeof(double2) * kTwN));
+        HZ_TRY(S.d_tw.reserve(2 * (size_t)kTwN));
         HZ_TRY_HIP(hipMemcpy(S.d_tw, tw.data(), sizeof(double2) * kTwN, hipMemcpyHostToDevice));
     }
     return HZ_OK;
@@ -1090,16 +1081,16 @@ StreamArgs stream_args(hz_fb* h) {
     a.R = S.R;
     a.wpos = ring_index(S, S.pos);
     a.prev = ring_index(S, S.pos - kSP);
-    a.HS = (const double2*)S.d_HS;
-    a.ZS = (double2*)S.d_ZS;
+    a.HS = (const double2*)S.d_HS.get();
+    a.ZS = (double2*)S.d_ZS.get();
     a.Q = (int)(S.K1 / kSP);
     a.head = S.head;
-    a.tw = (const double2*)S.d_tw;
+    a.tw = (const double2*)S.d_tw.get();
     a.h = h->resp.d_h;
     // C_b in parity b, R_b in parity b (block counter blk): this launch reads C_b, R_{b+1} and
     // writes C_{b+1}, R_{b+2}
     const size_t col = (size_t)kCols * 32;
-    double2* C = (double2*)S.d_CR;
+    double2* C = (double2*)S.d_CR.get();
     double2* Rb = C + 2 * col;
     const int b = (int)(S.blk & 1);
     a.Cin = C + b * col;
@@ -1123,10 +1114,10 @@ StreamArgs stream_args(hz_fb* h) {
 void d_args(hz_fb* h, StreamArgs* a) {
     hz_fb::Resp::Stream& S = h->resp.st;
     const size_t col = (size_t)kCols * 32;
-    double2* C = (double2*)S.d_CRD;
+    double2* C = (double2*)S.d_CRD.get();
     double2* Rb = C + 2 * col;
     const int b = (int)(S.blk & 1);
-    a->HSD = (const double2*)S.d_HSD;
+    a->HSD = (const double2*)S.d_HSD.get();
     a->hD = S.d_hD;
     a->CDin = C + b * col;
     a->CDout = C + (b ^ 1) * col;
@@ -1206,7 +1197,7 @@ unsigned long long* trace_slot(hz_fb* h, int kind) {
     static const bool on = getenv("HZ_STREAM_TRACE") != nullptr;
     if (!on) return nullptr;
     hz_fb::Resp::Stream& S = h->resp.st;
-    if (!S.d_trace && hipMalloc(&S.d_trace, sizeof(unsigned long long) * kTraceN * 1024) != hipSuccess) return nullptr;
+    if (S.d_trace.reserve((size_t)kTraceN * 1024) != HZ_OK) return nullptr;
     if (S.trace_n == kTraceN) trace_flush(h);
     const int i = S.trace_n++;
     S.trace_kind[i] = kind;
@@ -1253,7 +1244,7 @@ int fb_launch_stream(hz_fb* h, const double* d_in, double* d_out, long n) {
         const size_t col = (size_t)kCols * 32 * 2;
         HZ_TRY_HIP(hipMemsetAsync(S.d_HS + (size_t)Q * col, 0, sizeof(double) * 8 * col, h->stream));
         hipLaunchKernelGGL(stream_hs_kernel, dim3(kCols, (unsigned)Q), dim3(kT), 0, h->stream, (const double*)R.d_h,
-                           (const double2*)S.d_tw, (double2*)S.d_HS);
+                           (const double2*)S.d_tw.get(), (double2*)S.d_HS.get());
         HZ_TRY_HIP(hipGetLastError());
         if (S.tail) {
             HZ_TRY(tail_quiet(S));
@@ -1491,20 +1482,20 @@ int fb_stream_gain_setter(hz_fb* h) {
     const size_t col = (size_t)kCols * 32 * 2;
     const int Q = (int)(K / kSP);
     if (Q % 8 || Q / 8 > 16) return 0;   // (stream_setter_kernel: p = g + 8 i over QI = Q / 8)
-    if (s_alloc(&S.d_r0, &S.r0_cap, (size_t)N * kSP) != HZ_OK ||
-        s_alloc(&S.d_phi, &S.phi_cap, (size_t)N * O * kSP) != HZ_OK ||
-        s_alloc(&S.d_st, &S.st_cap, (size_t)N * Q * O) != HZ_OK ||
-        s_alloc(&S.d_rsp, &S.rsp_cap, (size_t)N * (O + 1) * col) != HZ_OK ||
-        s_alloc(&S.d_hD, &S.hD_cap, (size_t)K) != HZ_OK)
+    if (S.d_r0.reserve((size_t)N * kSP) != HZ_OK ||
+        S.d_phi.reserve((size_t)N * O * kSP) != HZ_OK ||
+        S.d_st.reserve((size_t)N * Q * O) != HZ_OK ||
+        S.d_rsp.reserve((size_t)N * (O + 1) * col) != HZ_OK ||
+        S.d_hD.reserve((size_t)K) != HZ_OK)
         return 0;
-    const size_t hcap = S.hsd_cap;
-    if (s_alloc(&S.d_HSD, &S.hsd_cap, (size_t)(Q + 8) * col) != HZ_OK) return 0;   // rows past Q stay zero
-    if (S.hsd_cap != hcap && hipMemset(S.d_HSD, 0, sizeof(double) * S.hsd_cap) != hipSuccess) return 0;
-    if (!S.d_CRD && hipMalloc(&S.d_CRD, sizeof(double) * 4 * col) != hipSuccess) return 0;
+    const size_t hcap = S.d_HSD.cap();
+    if (S.d_HSD.reserve((size_t)(Q + 8) * col) != HZ_OK) return 0;   // rows past Q stay zero
+    if (S.d_HSD.cap() != hcap && hipMemset(S.d_HSD, 0, sizeof(double) * S.d_HSD.cap()) != hipSuccess) return 0;
+    if (S.d_CRD.reserve(4 * col) != HZ_OK) return 0;
     if (S.sgpow_of != h->sg) {
         std::vector<double> sp(kSP);
         for (int j = 0; j < kSP; ++j) sp[j] = (double)powl((long double)h->sg, (long double)j);
-        if (!S.d_sgpow && hipMalloc(&S.d_sgpow, sizeof(double) * kSP) != hipSuccess) return 0;
+        if (S.d_sgpow.reserve(kSP) != HZ_OK) return 0;
         if (hipMemcpy(S.d_sgpow, sp.data(), sizeof(double) * kSP, hipMemcpyHostToDevice) != hipSuccess) return 0;
         S.sgpow_of = h->sg;
     }
@@ -1520,7 +1511,7 @@ int fb_stream_gain_setter(hz_fb* h) {
         default: hipLaunchKernelGGL(stream_rbasis_kernel<4>, g, dim3(128), 0, h->stream, F, Bc, pin, Q, S.d_r0, S.d_phi, S.d_st); break;
         }
         hipLaunchKernelGGL(stream_rspec_kernel, dim3(kCols, (unsigned)(O + 1), (unsigned)N), dim3(kT), 0, h->stream,
-                           (const double*)S.d_r0, (const double*)S.d_phi, O, (const double2*)S.d_tw, (double2*)S.d_rsp);
+                           (const double*)S.d_r0, (const double*)S.d_phi, O, (const double2*)S.d_tw.get(), (double2*)S.d_rsp.get());
         HZ_TRY_HIP(hipGetLastError());
         S.rband_valid = true;
     }
@@ -1536,7 +1527,7 @@ int fb_stream_gain_setter(hz_fb* h) {
     sa.r0 = S.d_r0;
     sa.phi = S.d_phi;
     sa.st = S.d_st;
-    sa.sp = (const double2*)S.d_rsp;
+    sa.sp = (const double2*)S.d_rsp.get();
     sa.K = K;
     sa.Q = Q;
     sa.O = O;
@@ -1544,11 +1535,11 @@ int fb_stream_gain_setter(hz_fb* h) {
     sa.dfirst = dfirst ? 1 : 0;
     sa.h = R.d_h;
     sa.hD = S.d_hD;
-    sa.HS = (double2*)S.d_HS;
-    sa.HSD = (double2*)S.d_HSD;
-    sa.ZS = (const double2*)S.d_ZS;
+    sa.HS = (double2*)S.d_HS.get();
+    sa.HSD = (double2*)S.d_HSD.get();
+    sa.ZS = (const double2*)S.d_ZS.get();
     sa.head = S.head;
-    sa.tw = (const double2*)S.d_tw;
+    sa.tw = (const double2*)S.d_tw.get();
     sa.C = ap.Cout;
     sa.R = ap.Rout;
     sa.CD = ap.CDout;
@@ -1595,16 +1586,11 @@ void fb_stream_free(hz_fb* h) {
     hz_fb::Resp::Stream& S = h->resp.st;
     (void)tail_quiet(S);
     trace_flush(h);
-    if (S.d_trace) (void)hipFree(S.d_trace);
-    S.d_trace = nullptr;
-    for (double* p : {S.d_line, S.d_ZS, S.d_HS, S.d_CR, S.d_tw, S.d_tH, S.d_tZ, S.d_tY, S.d_tout, S.d_hD, S.d_HSD,
-                      S.d_CRD, S.d_r0, S.d_phi, S.d_st, S.d_rsp, S.d_sgpow})
-        if (p) (void)hipFree(p);
     for (hipEvent_t e : {S.ev_main, S.ev_tail[0], S.ev_tail[1]})
         if (e) (void)hipEventDestroy(e);
     if (S.side) (void)hipStreamDestroy(S.side);
     const bool on = S.on;
-    S = hz_fb::Resp::Stream();
+    S = hz_fb::Resp::Stream();   // (frees the buffers)
     S.on = on;
 }
 

@@ -472,12 +472,7 @@ int hz_fb_process_tv_device(hz_fb* h, const double* d_in, double* d_out, size_t 
     const long chunk = std::max(1L, std::min(1L << 20, kPartBytes / (long)sizeof(double) / G));
     const long row = kind == HZ_FB_TV_COEFFS ? (2 * O + 1) * N : N;
     const long need = G * std::min((long)n, chunk);
-    if ((size_t)need > h->partial_cap) {
-        if (h->d_partial) HZ_TRY_HIP(hipFree(h->d_partial));
-        h->d_partial = nullptr;
-        HZ_TRY_HIP(hipMalloc(&h->d_partial, sizeof(double) * need));
-        h->partial_cap = need;
-    }
+    HZ_TRY(h->d_partial.reserve((size_t)need));
     const tv_fn k = tv_pick(O, kind, h->dist_id);
     for (long off = 0; off < (long)n; off += chunk) {
         const long len = std::min(chunk, (long)n - off);
@@ -531,13 +526,7 @@ int hz_fb_process_tv_device(hz_fb* h, const double* d_in, double* d_out, size_t 
     h->spare_ok = n == 1;   // see hz_fb_tick
     // the coefficients last set (the stream's final row) stay staged for later calls: copied
     // back without blocking, turned into F/B by fb_tv_materialize when next needed
-    if ((size_t)row > h->tv_row_cap) {
-        if (h->tv_row) HZ_TRY_HIP(hipHostFree(h->tv_row));
-        h->tv_row = nullptr;
-        h->tv_row_cap = 0;
-        HZ_TRY_HIP(hipHostMalloc(&h->tv_row, sizeof(double) * row, hipHostMallocDefault));
-        h->tv_row_cap = row;
-    }
+    HZ_TRY(h->tv_row.reserve((size_t)row));
     if (!h->tv_ev) HZ_TRY_HIP(hipEventCreateWithFlags(&h->tv_ev, hipEventDisableTiming));
     HZ_TRY_HIP(hipMemcpyAsync(h->tv_row, d_stream + ((long)n - 1) * row, sizeof(double) * row,
                               hipMemcpyDeviceToHost, h->stream));
@@ -563,10 +552,9 @@ int hz_fb_process_tv(hz_fb* h, const double* in, double* out, size_t n, int kind
         return HZ_E_INVALID;
     }
     const size_t row = kind == HZ_FB_TV_COEFFS ? (size_t)(2 * h->order + 1) * h->N : (size_t)h->N;
-    double *d_x = nullptr, *d_y = nullptr, *d_s = nullptr;
+    hz::DevBuf<double> d_x, d_y, d_s;
     int rc = HZ_OK;
-    if (hipMalloc(&d_x, sizeof(double) * n) != hipSuccess || hipMalloc(&d_y, sizeof(double) * n) != hipSuccess ||
-        hipMalloc(&d_s, sizeof(double) * n * row) != hipSuccess) {
+    if (d_x.reserve(n) || d_y.reserve(n) || d_s.reserve(n * row)) {
         hz::set_error("hz_fb_process_tv: device allocation failed (%zu stream doubles)", n * row);
         rc = HZ_E_ALLOC;
     }
@@ -585,9 +573,7 @@ int hz_fb_process_tv(hz_fb* h, const double* in, double* out, size_t n, int kind
         hz::set_error("hz_fb_process_tv: download failed");
         rc = HZ_E_HIP;
     }
-    (void)hipStreamSynchronize(h->stream);
-    for (double* p : {d_x, d_y, d_s})
-        if (p) (void)hipFree(p);
+    (void)hipStreamSynchronize(h->stream);   // before the temporaries go
     return rc;
 }
 

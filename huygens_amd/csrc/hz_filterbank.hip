@@ -772,12 +772,7 @@ int fb_launch_general(hz_fb* h, const double* d_in, double* d_out, long n) {
     const long chunk = fb_max_chunk(h);
     const long n_pad_max = std::min<long>(((n + kTile - 1) / kTile) * kTile, chunk);
     const size_t need = (size_t)G * n_pad_max;
-    if (need > h->partial_cap) {
-        if (h->d_partial) HZ_TRY_HIP(hipFree(h->d_partial));
-        h->d_partial = nullptr;
-        HZ_TRY_HIP(hipMalloc(&h->d_partial, sizeof(double) * need));
-        h->partial_cap = need;
-    }
+    HZ_TRY(h->d_partial.reserve(need));
     MixKernel kmix = pick_kernel(O, h->dist_id, h->waves, h->bands_per_wave, MODE_MIX);
     MixKernel kend = pick_kernel(O, h->dist_id, h->waves, h->bands_per_wave, MODE_SEGEND);
     HZ_TRY(fb_set_lds_attr((const void*)kmix));
@@ -790,15 +785,7 @@ int fb_launch_general(hz_fb* h, const double* d_in, double* d_out, long n) {
         long nseg = std::max<long>(1, std::min<long>(ntiles, (h->target_groups + G - 1) / G));
         const long seg_tiles = (ntiles + nseg - 1) / nseg;
         nseg = (ntiles + seg_tiles - 1) / seg_tiles;
-        if (nseg > 1 && O > 0) {
-            const size_t sneed = (size_t)h->N * nseg * O;
-            if (sneed > h->seg_cap) {
-                if (h->d_seg) HZ_TRY_HIP(hipFree(h->d_seg));
-                h->d_seg = nullptr;
-                HZ_TRY_HIP(hipMalloc(&h->d_seg, sizeof(double) * sneed));
-                h->seg_cap = sneed;
-            }
-        }
+        if (nseg > 1 && O > 0) HZ_TRY(h->d_seg.reserve((size_t)h->N * nseg * O));
         MixArgs a;
         a.rec = h->d_rec;
         a.pin = h->d_pin;
@@ -1019,15 +1006,9 @@ int hz_fb_create_shard(int order, int N_total, int band_begin, int band_count, d
             h->target_groups = prop.multiProcessorCount;
     }
     const int O = std::max(order, 1);
-    if (hipMalloc(&h->d_rec, sizeof(double) * N * h->rec) != hipSuccess ||
-        hipMalloc(&h->d_pin, sizeof(double) * N) != hipSuccess ||
-        hipMalloc(&h->d_gin, sizeof(double) * N) != hipSuccess ||
-        hipMalloc(&h->d_ystate[0], sizeof(double) * N * O) != hipSuccess ||
-        hipMalloc(&h->d_ystate[1], sizeof(double) * N * O) != hipSuccess ||
-        hipMalloc(&h->d_pg[0], sizeof(double) * N * 2) != hipSuccess ||
-        hipMalloc(&h->d_pg[1], sizeof(double) * N * 2) != hipSuccess ||
-        hipMalloc(&h->d_xhist[0], sizeof(double) * O) != hipSuccess ||
-        hipMalloc(&h->d_xhist[1], sizeof(double) * O) != hipSuccess) {
+    if (h->d_rec.reserve(N * h->rec) || h->d_pin.reserve(N) || h->d_gin.reserve(N) || h->d_ystate[0].reserve(N * O) ||
+        h->d_ystate[1].reserve(N * O) || h->d_pg[0].reserve(N * 2) || h->d_pg[1].reserve(N * 2) ||
+        h->d_xhist[0].reserve(O) || h->d_xhist[1].reserve(O)) {
         hz::set_error("hipMalloc failed for filterbank state (%zu bands)", N);
         return fail(HZ_E_ALLOC);
     }
@@ -1055,21 +1036,10 @@ int hz_fb_destroy(hz_fb* h) {
     h->rt.pending_ticks = 0;
     (void)hz_fbi::fb_rt_stop(h);   // the resident per-sample kernel leaves before the buffers go
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    hz_fbi::fb_rt_free(h);
-    for (double* p : {h->d_rec, h->d_pin, h->d_gin, h->d_ystate[0], h->d_ystate[1], h->d_pg[0], h->d_pg[1],
-                      h->d_xhist[0], h->d_xhist[1],
-                      h->d_partial, h->d_seg, h->d_in, h->d_out})
-        if (p) (void)hipFree(p);
-    for (auto& st : h->lti_set)
-        for (double* p : {st.d_rec, st.d_fmix, st.d_kt})
-            if (p) (void)hipFree(p);
     if (h->stream_red) (void)hipStreamSynchronize(h->stream_red);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : h->sync_ev) (void)hipEventDestroy(e);
     if (h->stream_red) (void)hipStreamDestroy(h->stream_red);
-    if (h->d_xhist_red) (void)hipFree(h->d_xhist_red);
-    if (h->tv_row) (void)hipHostFree(h->tv_row);
-    if (h->pin_io) (void)hipHostFree(h->pin_io);
     if (h->tv_ev) (void)hipEventDestroy(h->tv_ev);
     hz_fbi::fb_resp_free(h);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -1236,14 +1206,8 @@ int hz_fb_process(hz_fb* h, const double* in, double* out, size_t n) {
         if (--n == 0) return HZ_OK;
     }
     HZ_TRY(fb_check(h));
-    if (n > h->io_cap) {
-        if (h->d_in) HZ_TRY_HIP(hipFree(h->d_in));
-        if (h->d_out) HZ_TRY_HIP(hipFree(h->d_out));
-        h->d_in = h->d_out = nullptr;
-        HZ_TRY_HIP(hipMalloc(&h->d_in, sizeof(double) * n));
-        HZ_TRY_HIP(hipMalloc(&h->d_out, sizeof(double) * n));
-        h->io_cap = n;
-    }
+    HZ_TRY(h->d_in.reserve(n));
+    HZ_TRY(h->d_out.reserve(n));
     HZ_TRY(fb_upload(h));
     // a block the streaming engine takes (the reference's 1024-sample callback): its one kernel is
     // the only reader of the input and writer of the output, so it reads and writes pinned,
@@ -1252,8 +1216,7 @@ int hz_fb_process(hz_fb* h, const double* in, double* out, size_t n) {
         fb_stream_eligible(h, (long)n, h->order > 0 && fb_converged(h))) {
         const int nwg = hz_fbi::fb_stream_workgroups();
         if (!h->pin_io) {
-            HZ_TRY_HIP(hipHostMalloc((void**)&h->pin_io, sizeof(double) * (2 * kStreamBlock + 256),
-                                     hipHostMallocCoherent | hipHostMallocMapped));
+            HZ_TRY(h->pin_io.reserve(2 * kStreamBlock + 256));
             std::memset(h->pin_io + 2 * kStreamBlock, 0, sizeof(double) * 256);
         }
         void* dio = nullptr;

@@ -239,24 +239,19 @@ struct hz_frz {
     long u0 = 0;                  // start of the current unfrozen stretch (the Delay ring snapshot is at u0)
     long mask = 0;
     long chunk = 0;               // samples per chunk (kChunk; env HZ_FRZ_CHUNK at create, tests)
-    double *d_ring = nullptr, *d_win = nullptr, *d_norm = nullptr, *d_phase = nullptr, *d_ifstate = nullptr;
-    double* d_ifopen = nullptr;   // [M][N] IFrames of the freeze period open at chunk start
-    double *d_dnorm = nullptr, *d_dphase = nullptr;   // [M][N] DFrame state (persists across freezes)
-    double* d_ifnew = nullptr;    // [P][M][N] IFrames of the chunk's freezes
-    size_t ifnew_cap = 0;         // periods
-    double* d_snap = nullptr;     // [S][N+1]; snapshot 0 = the ring at u0
-    size_t snap_cap = 0;
-    double2* d_tw = nullptr;
-    void* d_tab = nullptr;        // runs + maps + stretches of one chunk
+    hz::DevBuf<double> d_ring, d_win, d_norm, d_phase, d_ifstate;
+    hz::DevBuf<double> d_ifopen;  // [M][N] IFrames of the freeze period open at chunk start
+    hz::DevBuf<double> d_dnorm, d_dphase;   // [M][N] DFrame state (persists across freezes)
+    hz::DevBuf<double> d_ifnew;   // [P][M][N] IFrames of the chunk's freezes
+    hz::DevBuf<double> d_snap;    // [S][N+1]; snapshot 0 = the ring at u0
+    hz::DevBuf<double2> d_tw;
+    hz::DevBuf<char> d_tab;       // runs + maps + stretches of one chunk
     // host side of the chunk tables, kept across chunks (capacity reused: no regrowth copies); the
     // upload goes from pinned staging (an async DMA, no bounce copy)
     std::vector<FrzRun> v_runs;
     std::vector<SlotSrc> v_maps;
-    char* h_tab = nullptr;        // pinned
-    size_t h_tab_cap = 0;
-    size_t tab_cap = 0;
-    double *d_in = nullptr, *d_out = nullptr;
-    size_t in_cap = 0, out_cap = 0;
+    hz::PinBuf<char> h_tab;
+    hz::DevBuf<double> d_in, d_out;
     hipStream_t stream = nullptr;
     bool own_stream = false;
     bool prof = false;                 // HIP events around each frz_out_kernel launch
@@ -273,16 +268,6 @@ int frz_check(hz_frz* h) {
         return HZ_E_INVALID;
     }
     HZ_TRY_HIP(hipSetDevice(h->device));
-    return HZ_OK;
-}
-
-int grow(void** p, size_t* cap, size_t bytes, hipStream_t st) {
-    if (bytes <= *cap) return HZ_OK;
-    HZ_TRY_HIP(hipStreamSynchronize(st));
-    if (*p) HZ_TRY_HIP(hipFree(*p));
-    *p = nullptr;
-    HZ_TRY_HIP(hipMalloc(p, bytes));
-    *cap = bytes;
     return HZ_OK;
 }
 
@@ -353,7 +338,9 @@ int frz_chunk(hz_frz* h, const double* d_in, double* d_out, long n, const hz_frz
         }
     }
     const int P = (int)pre_tf.size();
-    HZ_TRY(grow((void**)&h->d_ifnew, &h->ifnew_cap, sizeof(double) * (size_t)std::max(1, P) * M * N, h->stream));
+    const size_t n_ifnew = (size_t)std::max(1, P) * M * N;
+    if (n_ifnew > h->d_ifnew.cap()) HZ_TRY_HIP(hipStreamSynchronize(h->stream));
+    HZ_TRY(h->d_ifnew.reserve(n_ifnew));
     const size_t lds = sizeof(double) * 2 * N;
     const int ft = std::min(kThreads, std::max(64, N / 4));   // within the kernels' launch bounds
     for (int q = 0; q < P; ++q) {   // new period q is source q + 1
@@ -424,15 +411,11 @@ int frz_chunk(hz_frz* h, const double* d_in, double* d_out, long n, const hz_frz
     const size_t nsnap = stretch.size() / 2 + 1;
     const long nb = (n + kThreads - 1) / kThreads;
     const size_t b_blk = sizeof(int) * (size_t)(nb + 1), b_src = sizeof(int) * (size_t)M;
-    HZ_TRY(grow(&h->d_tab, &h->tab_cap, b_runs + b_maps + b_st + b_blk + b_src + 64, h->stream));
     const size_t b_tab = b_runs + b_maps + b_st + b_blk + b_src;
-    if (b_tab > h->h_tab_cap) {   // (the previous chunk's upload finished: every chunk ends synchronised)
-        if (h->h_tab) HZ_TRY_HIP(hipHostFree(h->h_tab));
-        h->h_tab = nullptr;
-        h->h_tab_cap = 0;
-        HZ_TRY_HIP(hipHostMalloc((void**)&h->h_tab, b_tab * 2));
-        h->h_tab_cap = b_tab * 2;
-    }
+    if (b_tab + 64 > h->d_tab.cap()) HZ_TRY_HIP(hipStreamSynchronize(h->stream));
+    HZ_TRY(h->d_tab.reserve(b_tab + 64));
+    // (the previous chunk's upload finished: every chunk ends synchronised)
+    if (b_tab > h->h_tab.cap()) HZ_TRY(h->h_tab.reserve(b_tab * 2));
     char* hb = h->h_tab;
     std::memcpy(hb, runs.data(), b_runs);
     if (!maps.empty()) std::memcpy(hb + b_runs, maps.data(), maps.size() * sizeof(SlotSrc));
@@ -449,14 +432,12 @@ int frz_chunk(hz_frz* h, const double* d_in, double* d_out, long n, const hz_frz
     HZ_TRY_HIP(hipMemcpyAsync(h->d_tab, hb, b_tab, hipMemcpyHostToDevice, h->stream));
     const char* tab = (const char*)h->d_tab;
     // Delay ring snapshots after each dry stretch that ended here
-    if (nsnap > h->snap_cap / (sizeof(double) * (N + 1))) {
-        double* ns = nullptr;
+    if (nsnap > h->d_snap.cap() / (N + 1)) {   // grows keeping snapshot 0
+        hz::DevBuf<double> ns;
         HZ_TRY_HIP(hipStreamSynchronize(h->stream));
-        HZ_TRY_HIP(hipMalloc(&ns, sizeof(double) * (N + 1) * nsnap));
+        HZ_TRY(ns.reserve((size_t)(N + 1) * nsnap));
         HZ_TRY_HIP(hipMemcpy(ns, h->d_snap, sizeof(double) * (N + 1), hipMemcpyDeviceToDevice));
-        HZ_TRY_HIP(hipFree(h->d_snap));
-        h->d_snap = ns;
-        h->snap_cap = sizeof(double) * (N + 1) * nsnap;
+        h->d_snap = std::move(ns);
     }
     if (nsnap > 1) {
         hipLaunchKernelGGL(frz_snap_kernel, dim3((N + 1 + 255) / 256), dim3(256), 0, h->stream, d_in, T0,
@@ -567,19 +548,13 @@ int hz_frz_create(int N, int laps, double width, int device, hz_frz** out) {
     }
     const size_t MN = (size_t)h->M * N;
     bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_ring, sizeof(double) * H) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_win, sizeof(double) * N) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_tw, sizeof(double2) * (N / 2)) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_norm, sizeof(double) * MN) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_phase, sizeof(double) * MN) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_ifstate, sizeof(double) * MN) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_ifopen, sizeof(double) * MN) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_dnorm, sizeof(double) * MN) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_dphase, sizeof(double) * MN) == hipSuccess;
+    ok = ok && h->d_ring.reserve(H) == HZ_OK && h->d_win.reserve(N) == HZ_OK && h->d_tw.reserve(N / 2) == HZ_OK;
+    ok = ok && h->d_norm.reserve(MN) == HZ_OK && h->d_phase.reserve(MN) == HZ_OK;
+    ok = ok && h->d_ifstate.reserve(MN) == HZ_OK && h->d_ifopen.reserve(MN) == HZ_OK;
+    ok = ok && h->d_dnorm.reserve(MN) == HZ_OK && h->d_dphase.reserve(MN) == HZ_OK;
     ok = ok && hipMemset(h->d_dnorm, 0, sizeof(double) * MN) == hipSuccess;   // reference: uninitialised
     ok = ok && hipMemset(h->d_dphase, 0, sizeof(double) * MN) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_snap, sizeof(double) * (N + 1)) == hipSuccess;
-    if (ok) h->snap_cap = sizeof(double) * (N + 1);
+    ok = ok && h->d_snap.reserve(N + 1) == HZ_OK;
     ok = ok && hipMemset(h->d_ring, 0, sizeof(double) * H) == hipSuccess;
     ok = ok && hipMemset(h->d_ifstate, 0, sizeof(double) * MN) == hipSuccess;   // IFrame data zeroed (fourier.h:308)
     ok = ok && hipMemset(h->d_ifopen, 0, sizeof(double) * MN) == hipSuccess;
@@ -597,10 +572,6 @@ int hz_frz_create(int N, int laps, double width, int device, hz_frz** out) {
     }
     if (!ok) {
         hz::set_error("hz_frz_create: device allocation failed");
-        for (void* p : {(void*)h->d_ring, (void*)h->d_win, (void*)h->d_tw, (void*)h->d_norm, (void*)h->d_phase,
-                        (void*)h->d_ifstate, (void*)h->d_ifopen, (void*)h->d_dnorm, (void*)h->d_dphase,
-                        (void*)h->d_snap})
-            if (p) (void)hipFree(p);
         if (h->stream) (void)hipStreamDestroy(h->stream);
         delete h;
         return HZ_E_ALLOC;
@@ -614,12 +585,6 @@ int hz_frz_destroy(hz_frz* h) {
     if (!h) return HZ_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void* p : {(void*)h->d_ring, (void*)h->d_win, (void*)h->d_tw, (void*)h->d_norm, (void*)h->d_phase,
-                    (void*)h->d_ifstate, (void*)h->d_ifopen, (void*)h->d_dnorm, (void*)h->d_dphase,
-                    (void*)h->d_ifnew, (void*)h->d_snap, h->d_tab, (void*)h->d_in,
-                    (void*)h->d_out})
-        if (p) (void)hipFree(p);
-    if (h->h_tab) (void)hipHostFree(h->h_tab);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -685,8 +650,10 @@ int hz_frz_process(hz_frz* h, const double* in, double* out, size_t n, const hz_
     HZ_TRY(frz_check(h));
     if ((n && (!in || !out)) || nev < 0 || (nev && !ev)) return HZ_E_INVALID;
     if (n) {
-        HZ_TRY(grow((void**)&h->d_in, &h->in_cap, sizeof(double) * n, h->stream));
-        HZ_TRY(grow((void**)&h->d_out, &h->out_cap, sizeof(double) * n, h->stream));
+        for (hz::DevBuf<double>* b : {&h->d_in, &h->d_out}) {
+            if (n > b->cap()) HZ_TRY_HIP(hipStreamSynchronize(h->stream));
+            HZ_TRY(b->reserve(n));
+        }
         HZ_TRY_HIP(hipMemcpyAsync(h->d_in, in, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
     }
     HZ_TRY(hz_frz_process_device(h, h->d_in, h->d_out, n, ev, nev));

@@ -151,15 +151,12 @@ struct hz_gran {
     unsigned leaves = 1;
     std::vector<std::deque<GrainDev>> vg;   // per voice, its grains that may still read, in time order
     long mask = 0;
-    double* d_ring = nullptr;
-    GrainDev* d_g = nullptr;          // the call's grains + tile lists (bytes)
-    size_t g_cap = 0;
-    GrainDev* h_g = nullptr;          // pinned staging of the same (bytes)
-    size_t hg_cap = 0;
+    hz::DevBuf<double> d_ring;
+    hz::DevBuf<char> d_g;             // the call's grains (GrainDev) + tile lists (bytes)
+    hz::PinBuf<char> h_g;             // pinned staging of the same
     hipEvent_t up_ev = nullptr;
     bool up_pending = false;
-    double *d_in = nullptr, *d_out = nullptr;
-    size_t io_cap = 0;
+    hz::DevBuf<double> d_in, d_out;
     hipStream_t stream = nullptr;
     bool own_stream = false;
     bool prof = false;
@@ -169,8 +166,7 @@ struct hz_gran {
     bool pending = false;             // block work queued on the stream since the last synchronisation
     // per-sample calls (hz_gran_sample): the grains that may still read, in voice order, in pinned
     // memory for the server (which caches them by version)
-    GrainDev* h_list = nullptr;
-    size_t list_cap = 0;
+    hz::PinBuf<GrainDev> h_list{hipHostMallocCoherent | hipHostMallocMapped};
     int list_count = 0;
     long list_version = 0, list_min_end = 0;
     bool list_dirty = true;
@@ -223,15 +219,6 @@ int gran_alloc(hz_gran* h, long t, unsigned ticks0, double offset, double size, 
     return voice;
 }
 
-int ensure(double** p, size_t* cap, size_t n) {
-    if (n <= *cap) return HZ_OK;
-    if (*p) HZ_TRY_HIP(hipFree(*p));
-    *p = nullptr;
-    HZ_TRY_HIP(hipMalloc(p, n * sizeof(double)));
-    *cap = n;
-    return HZ_OK;
-}
-
 int gran_run(hz_gran* h, const double* d_in, double* d_out, long n, const hz_grain_req* reqs, int nreq, int* voices) {
     if (n <= 0 && nreq > 0) {
         hz::set_error("hz_gran_process: requests need n > 0 (use hz_gran_request between calls)");
@@ -278,20 +265,10 @@ int gran_run(hz_gran* h, const double* d_in, double* d_out, long n, const hz_gra
     const size_t b_rec = recs.size() * sizeof(GrainDev), b_off = cnt.size() * sizeof(int);
     const size_t bytes = b_rec + b_off + idx.size() * sizeof(int);
     if (h->up_pending) HZ_TRY_HIP(hipEventSynchronize(h->up_ev));   // staging buffer reuse
-    if (bytes > h->hg_cap) {
-        if (h->h_g) HZ_TRY_HIP(hipHostFree(h->h_g));
-        h->h_g = nullptr;
-        const size_t cap = std::max<size_t>(bytes, 2 * h->hg_cap);
-        HZ_TRY_HIP(hipHostMalloc((void**)&h->h_g, cap));
-        h->hg_cap = cap;
-    }
-    if (bytes > h->g_cap) {
+    if (bytes > h->h_g.cap()) HZ_TRY(h->h_g.reserve(std::max<size_t>(bytes, 2 * h->h_g.cap())));
+    if (bytes > h->d_g.cap()) {
         HZ_TRY_HIP(hipStreamSynchronize(h->stream));
-        if (h->d_g) HZ_TRY_HIP(hipFree(h->d_g));
-        h->d_g = nullptr;
-        const size_t cap = std::max<size_t>(bytes, 2 * h->g_cap);
-        HZ_TRY_HIP(hipMalloc((void**)&h->d_g, cap));
-        h->g_cap = cap;
+        HZ_TRY(h->d_g.reserve(std::max<size_t>(bytes, 2 * h->d_g.cap())));
     }
     char* hs = (char*)h->h_g;
     std::memcpy(hs, recs.data(), b_rec);
@@ -382,13 +359,12 @@ int hz_gran_create(unsigned polyphony, unsigned buffer_size, int device, hz_gran
     h->mask = C - 1;
     bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&h->up_ev, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_ring, sizeof(double) * C) == hipSuccess;
+    ok = ok && h->d_ring.reserve(C) == HZ_OK;
     ok = ok && hipMemset(h->d_ring, 0, sizeof(double) * C) == hipSuccess;   // Buffer: zeroed
     if (!ok) {
         hz::set_error("hz_gran_create: device allocation failed");
         if (h->up_ev) (void)hipEventDestroy(h->up_ev);
         if (h->stream) (void)hipStreamDestroy(h->stream);
-        if (h->d_ring) (void)hipFree(h->d_ring);
         delete h;
         return HZ_E_ALLOC;
     }
@@ -401,10 +377,6 @@ int hz_gran_destroy(hz_gran* h) {
     if (!h) return HZ_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void* p : {(void*)h->d_ring, (void*)h->d_g, (void*)h->d_in, (void*)h->d_out})
-        if (p) (void)hipFree(p);
-    if (h->h_g) (void)hipHostFree(h->h_g);
-    if (h->h_list) (void)hipHostFree(h->h_list);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     if (h->up_ev) (void)hipEventDestroy(h->up_ev);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -434,10 +406,8 @@ int hz_gran_process(hz_gran* h, const double* in, double* out, size_t n, const h
     HZ_TRY(gran_check(h));
     if ((n && (!in || !out)) || nreq < 0 || (nreq && !reqs)) return HZ_E_INVALID;
     if (n == 0) return gran_run(h, nullptr, nullptr, 0, reqs, nreq, voices);
-    size_t cap_in = h->io_cap, cap_out = h->io_cap;
-    HZ_TRY(ensure(&h->d_in, &cap_in, n));
-    HZ_TRY(ensure(&h->d_out, &cap_out, n));
-    h->io_cap = std::min(cap_in, cap_out);
+    HZ_TRY(h->d_in.reserve(n));
+    HZ_TRY(h->d_out.reserve(n));
     HZ_TRY_HIP(hipMemcpyAsync(h->d_in, in, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HZ_TRY(gran_run(h, h->d_in, h->d_out, (long)n, reqs, nreq, voices));
     HZ_TRY_HIP(hipMemcpyAsync(out, h->d_out, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -462,13 +432,7 @@ int hz_gran_sample(hz_gran* h, double x, double* y) {
         // the server caches the grain list in LDS (kMaxGrains); a denser texture takes the
         // one-sample block call, which has no such cap (the list stays dirty until it fits)
         if (cnt > (size_t)hz_rt::kMaxGrains) return hz_gran_process(h, &x, y, 1, nullptr, 0, nullptr);
-        if (cnt > h->list_cap || !h->h_list) {
-            if (h->h_list) HZ_TRY_HIP(hipHostFree(h->h_list));
-            h->h_list = nullptr;
-            h->list_cap = std::max<size_t>(cnt, 64);
-            HZ_TRY_HIP(hipHostMalloc((void**)&h->h_list, sizeof(GrainDev) * h->list_cap,
-                                     hipHostMallocCoherent | hipHostMallocMapped));
-        }
+        HZ_TRY(h->h_list.reserve(std::max<size_t>(cnt, 64)));
         long mn = kNever;
         int k = 0;
         for (const auto& q : h->vg)   // voice order (the reference's summation order)

@@ -322,14 +322,13 @@ struct hz_het {
     std::vector<double> w[2];             // host mirrors of the Oscbank frequencies (re, im interleaved)
     std::vector<unsigned char> act;       // [2][Np]
     bool w_dirty = false, act_dirty = false;
-    double* d_st = nullptr;               // [F_COUNT][Np]
-    double* d_ring = nullptr;             // [W1][Np]
-    unsigned char* d_act = nullptr;       // [2][Np]
-    unsigned char* d_latch = nullptr;     // [Np]
-    double* d_part = nullptr;
+    hz::DevBuf<double> d_st;              // [F_COUNT][Np]
+    hz::DevBuf<double> d_ring;            // [W1][Np]
+    hz::DevBuf<unsigned char> d_act;      // [2][Np]
+    hz::DevBuf<unsigned char> d_latch;    // [Np]
+    hz::DevBuf<double> d_part;
     long chunk = 0;                       // samples per launch pair
-    double *d_in = nullptr, *d_out = nullptr;
-    size_t io_cap = 0;
+    hz::DevBuf<double> d_in, d_out;
     hipStream_t stream = nullptr;
     bool own_stream = false;
     bool prof = false;
@@ -407,15 +406,6 @@ int het_setup(hz_het* h, int order, const double* radii) {
     HZ_TRY(upload_field(h, F_RI, im.data()));
     for (int f = F_SLIDE; f < F_SLIDE + 2 * kMaxOrder; ++f) HZ_TRY(upload_field(h, f, zero.data()));
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
-    return HZ_OK;
-}
-
-int ensure(double** p, size_t* cap, size_t n) {
-    if (n <= *cap) return HZ_OK;
-    if (*p) HZ_TRY_HIP(hipFree(*p));
-    *p = nullptr;
-    HZ_TRY_HIP(hipMalloc(p, n * sizeof(double)));
-    *cap = n;
     return HZ_OK;
 }
 
@@ -510,11 +500,11 @@ int hz_het_create(int channels, int order, const double* radii, double thresh, d
         h->chunk = std::max(1L, std::min(h->chunk, std::atol(e)));
     const size_t ring_bytes = sizeof(double) * (size_t)h->W1 * h->Np;
     bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_st, sizeof(double) * F_COUNT * h->Np) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_ring, ring_bytes) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_act, 2 * h->Np) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_latch, h->Np) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_part, sizeof(double) * h->G * h->chunk) == hipSuccess;
+    ok = ok && h->d_st.reserve((size_t)F_COUNT * h->Np) == HZ_OK;
+    ok = ok && h->d_ring.reserve((size_t)h->W1 * h->Np) == HZ_OK;
+    ok = ok && h->d_act.reserve(2 * (size_t)h->Np) == HZ_OK;
+    ok = ok && h->d_latch.reserve(h->Np) == HZ_OK;
+    ok = ok && h->d_part.reserve((size_t)h->G * h->chunk) == HZ_OK;
     ok = ok && hipMemset(h->d_st, 0, sizeof(double) * F_COUNT * h->Np) == hipSuccess;
     ok = ok && hipMemset(h->d_ring, 0, ring_bytes) == hipSuccess;
     ok = ok && hipMemset(h->d_act, 0, 2 * h->Np) == hipSuccess;
@@ -544,9 +534,6 @@ int hz_het_destroy(hz_het* h) {
     if (!h) return HZ_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void* p : {(void*)h->d_st, (void*)h->d_ring, (void*)h->d_act, (void*)h->d_latch, (void*)h->d_part,
-                    (void*)h->d_in, (void*)h->d_out})
-        if (p) (void)hipFree(p);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -603,10 +590,8 @@ int hz_het_process(hz_het* h, const double* in, double* out, size_t n) {
     HZ_TRY(het_check(h));
     if (n && (!in || !out)) return HZ_E_INVALID;
     if (n == 0) return HZ_OK;
-    size_t cap_in = h->io_cap, cap_out = h->io_cap;
-    HZ_TRY(ensure(&h->d_in, &cap_in, n));
-    HZ_TRY(ensure(&h->d_out, &cap_out, n));
-    h->io_cap = std::min(cap_in, cap_out);
+    HZ_TRY(h->d_in.reserve(n));
+    HZ_TRY(h->d_out.reserve(n));
     HZ_TRY_HIP(hipMemcpyAsync(h->d_in, in, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HZ_TRY(het_run(h, h->d_in, h->d_out, (long)n));
     HZ_TRY_HIP(hipMemcpyAsync(out, h->d_out, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));

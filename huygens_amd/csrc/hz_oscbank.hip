@@ -258,10 +258,9 @@ struct hz_osc {
     std::vector<double> h_rec;
     bool dirty_rec = true, dirty_act = true;
     std::vector<int> act;                     // ascending active local indices
-    double *d_rec = nullptr, *d_z = nullptr, *d_partial = nullptr, *d_mix = nullptr, *d_pb = nullptr;
-    int* d_act = nullptr;
-    unsigned char* d_active = nullptr;
-    size_t partial_cap = 0, mix_cap = 0, pb_cap = 0;
+    hz::DevBuf<double> d_rec, d_z, d_partial, d_mix, d_pb;
+    hz::DevBuf<int> d_act;
+    hz::DevBuf<unsigned char> d_active;
     int target_groups = 256;
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -274,9 +273,9 @@ struct hz_osc {
     // snapshot (an Oscbank has no input); setters roll the phasors back to the consumed sample
     // (huygens_hip.h, hz_add_fill)
     long la_L = 0, la_n = 0, la_pos = 0;
-    double *d_la_pb = nullptr, *d_la_mix = nullptr, *d_z_snap = nullptr;
-    double* la_mix = nullptr;          // pinned [la_L][2]
-    double* la_pb = nullptr;           // pinned [la_L][N][2] per-band rows (small banks: N la_L <= 2^18)
+    hz::DevBuf<double> d_la_pb, d_la_mix, d_z_snap;
+    hz::PinBuf<double> la_mix;         // pinned [la_L][2]
+    hz::PinBuf<double> la_pb;          // pinned [la_L][N][2] per-band rows (small banks: N la_L <= 2^18)
 };
 
 namespace {
@@ -349,12 +348,7 @@ int osc_launch(hz_osc* h, double* d_mix, double* d_per_band, long n) {
         nseg = (ntiles + seg_tiles - 1) / seg_tiles;
         const long n_pad = ntiles * kTile;
         const size_t need = (size_t)G * n_pad * 2;
-        if (need > h->partial_cap) {
-            if (h->d_partial) HZ_TRY_HIP(hipFree(h->d_partial));
-            h->d_partial = nullptr;
-            HZ_TRY_HIP(hipMalloc(&h->d_partial, sizeof(double) * need));
-            h->partial_cap = need;
-        }
+        HZ_TRY(h->d_partial.reserve(need));
         const size_t lds = sizeof(double) * (2 * kWaves * kL * kPad + kWaves * 2 * kMaxPerWave);
         static bool attr = false;
         if (!attr) {
@@ -376,7 +370,7 @@ int osc_launch(hz_osc* h, double* d_mix, double* d_per_band, long n) {
                            (const double*)h->d_rec, a);
         HZ_TRY_HIP(hipGetLastError());
         hipLaunchKernelGGL(osc_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, h->stream,
-                           (const double2*)h->d_partial, n_pad, G, n, (double2*)d_mix);
+                           (const double2*)h->d_partial.get(), n_pad, G, n, (double2*)d_mix);
         HZ_TRY_HIP(hipGetLastError());
     }
     if (e) HZ_TRY_HIP(hipEventRecord(e[1], h->stream));
@@ -403,12 +397,12 @@ int osc_settle(hz_osc* h) {
 int osc_look_ahead(hz_osc* h) {
     if (!h->la_L) {
         h->la_L = std::min<long>(1024, std::max<long>(16, (1L << 21) / std::max(1, h->N)));
-        HZ_TRY_HIP(hipMalloc(&h->d_la_pb, sizeof(double) * 2 * h->la_L * h->N));
-        HZ_TRY_HIP(hipMalloc(&h->d_la_mix, sizeof(double) * 2 * h->la_L));
-        HZ_TRY_HIP(hipMalloc(&h->d_z_snap, sizeof(double) * 2 * h->N));
-        HZ_TRY_HIP(hipHostMalloc((void**)&h->la_mix, sizeof(double) * 2 * h->la_L));
+        HZ_TRY(h->d_la_pb.reserve((size_t)2 * h->la_L * h->N));
+        HZ_TRY(h->d_la_mix.reserve((size_t)2 * h->la_L));
+        HZ_TRY(h->d_z_snap.reserve((size_t)2 * h->N));
+        HZ_TRY(h->la_mix.reserve((size_t)2 * h->la_L));
         if ((long)h->N * h->la_L <= (1L << 18))   // small banks: operator() reads host memory
-            HZ_TRY_HIP(hipHostMalloc((void**)&h->la_pb, sizeof(double) * 2 * h->la_L * h->N));
+            HZ_TRY(h->la_pb.reserve((size_t)2 * h->la_L * h->N));
     }
     HZ_TRY(osc_upload(h));
     HZ_TRY_HIP(hipMemcpyAsync(h->d_z_snap, h->d_z, sizeof(double) * 2 * h->N, hipMemcpyDeviceToDevice, h->stream));
@@ -453,10 +447,8 @@ int hz_osc_create_shard(int N_total, int begin, int count, double k, int device,
     };
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail(HZ_E_HIP);
     h->own_stream = true;
-    if (hipMalloc(&h->d_rec, sizeof(double) * count * ORec::SIZE) != hipSuccess ||
-        hipMalloc(&h->d_z, sizeof(double) * 2 * count) != hipSuccess ||
-        hipMalloc(&h->d_act, sizeof(int) * count) != hipSuccess ||
-        hipMalloc(&h->d_active, count) != hipSuccess) {
+    if (h->d_rec.reserve((size_t)count * ORec::SIZE) || h->d_z.reserve((size_t)2 * count) ||
+        h->d_act.reserve(count) || h->d_active.reserve(count)) {
         hz::set_error("hipMalloc failed for oscbank state");
         return fail(HZ_E_ALLOC);
     }
@@ -474,11 +466,6 @@ int hz_osc_destroy(hz_osc* h) {
     if (!h) return HZ_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void* p : {(void*)h->d_rec, (void*)h->d_z, (void*)h->d_partial, (void*)h->d_mix, (void*)h->d_pb,
-                    (void*)h->d_act, (void*)h->d_active, (void*)h->d_la_pb, (void*)h->d_la_mix, (void*)h->d_z_snap})
-        if (p) (void)hipFree(p);
-    if (h->la_mix) (void)hipHostFree(h->la_mix);
-    if (h->la_pb) (void)hipHostFree(h->la_pb);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -568,19 +555,9 @@ int hz_osc_fill(hz_osc* h, double* mix, double* per_band, size_t n) {
         return HZ_OK;
     }
     HZ_TRY(osc_settle(h));
-    if (mix && 2 * n > h->mix_cap) {
-        if (h->d_mix) HZ_TRY_HIP(hipFree(h->d_mix));
-        h->d_mix = nullptr;
-        HZ_TRY_HIP(hipMalloc(&h->d_mix, sizeof(double) * 2 * n));
-        h->mix_cap = 2 * n;
-    }
+    if (mix) HZ_TRY(h->d_mix.reserve(2 * n));
     const size_t pbn = 2 * n * (size_t)h->N;
-    if (per_band && pbn > h->pb_cap) {
-        if (h->d_pb) HZ_TRY_HIP(hipFree(h->d_pb));
-        h->d_pb = nullptr;
-        HZ_TRY_HIP(hipMalloc(&h->d_pb, sizeof(double) * pbn));
-        h->pb_cap = pbn;
-    }
+    if (per_band) HZ_TRY(h->d_pb.reserve(pbn));
     HZ_TRY(osc_upload(h));
     HZ_TRY(osc_launch(h, mix ? h->d_mix : nullptr, per_band ? h->d_pb : nullptr, (long)n));
     if (mix) HZ_TRY_HIP(hipMemcpyAsync(mix, h->d_mix, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, h->stream));

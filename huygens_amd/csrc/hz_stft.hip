@@ -1154,18 +1154,16 @@ struct hz_stft {
     hz_stft_proc host_proc = nullptr;
     long T = 0;        // samples processed
     long frames = 0;   // frames completed
-    double* d_win = nullptr;
-    double2 *d_tw = nullptr, *d_spec = nullptr;
-    double* d_fo = nullptr;                    // planar frame ring: Re [R][N], Im [R][N]
-    double* d_hist[2] = {nullptr, nullptr};    // last N-1 input samples, [Re | Im] (ping-pong)
+    hz::DevBuf<double> d_win;
+    hz::DevBuf<double2> d_tw, d_spec;
+    hz::DevBuf<double> d_fo;                   // planar frame ring: Re [R][N], Im [R][N]
+    hz::DevBuf<double> d_hist[2];              // last N-1 input samples, [Re | Im] (ping-pong)
     long last_cplx = -1;                       // last sample index that came with an imaginary part
     // frames >= im_zero_from came from the pair kernel, whose Im plane (all zeros) is not written:
     // the overlap-add reads no Im part for them (LONG_MAX: none since the last other launch)
     long im_zero_from = LONG_MAX;
     int hcur = 0;
-    size_t spec_cap = 0;
-    double *d_in = nullptr, *d_out = nullptr;
-    size_t io_cap = 0;
+    hz::DevBuf<double> d_in, d_out;            // host-buffer calls: [Re | Im]
     std::vector<double2> h_spec, h_out;   // host-processor path: spectra + per-slot out buffers
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -1186,7 +1184,7 @@ struct hz_stft {
     std::vector<int> s_wp, s_rp;
     std::vector<char> s_reading, s_writing;
     std::vector<double> h_win;
-    double2* d_slot = nullptr;   // [2][N] device scratch
+    hz::DevBuf<double2> d_slot;  // [2][N] device scratch
 };
 
 namespace {
@@ -1278,15 +1276,6 @@ int frames_fused(hz_stft* h, const StftArgs& a, long nf) {
     return HZ_OK;
 }
 
-int ensure_dev(void** p, size_t* cap, size_t bytes) {
-    if (bytes <= *cap) return HZ_OK;
-    if (*p) HZ_TRY_HIP(hipFree(*p));
-    *p = nullptr;
-    HZ_TRY_HIP(hipMalloc(p, bytes));
-    *cap = bytes;
-    return HZ_OK;
-}
-
 int stft_block(hz_stft* h, const double* d_re, const double* d_im, double* d_ore, double* d_oim, long n) {
     const int N = h->N;
     double* hc = h->d_hist[h->hcur];
@@ -1366,7 +1355,7 @@ int stft_block(hz_stft* h, const double* d_re, const double* d_im, double* d_ore
                 // several back-to-back launches: per-launch time without the event overhead
                 for (int r = 0; r < (h->prof ? h->prof_repeat : 1); ++r) HZ_TRY(frames_fused(h, a, nf));
             } else {
-                HZ_TRY(ensure_dev((void**)&h->d_spec, &h->spec_cap, sizeof(double2) * (size_t)nf * N));
+                HZ_TRY(h->d_spec.reserve((size_t)nf * N));
                 a.spec = h->d_spec;
                 launch_frames<HZ_PROC_IDENTITY, 1>(h, a, nf);
                 HZ_TRY_HIP(hipGetLastError());
@@ -1490,7 +1479,7 @@ int hz_stft_create(int N, int laps, int window, int proc, double p0, double p1, 
     h->h_win = win;
     const std::vector<double2> tw = twiddles(N);
     bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_win, sizeof(double) * N) == hipSuccess;
+    ok = ok && h->d_win.reserve(N) == HZ_OK;
     // N = 4096: the specialised pair kernel's pass tables after the N/2 table (p4::kTwLen)
     std::vector<double2> twx = tw;
     if (N == p4::kN) {   // W^((p << s) r) mod N, r = 1..7, in long double
@@ -1506,10 +1495,10 @@ int hz_stft_create(int N, int laps, int window, int proc, double p0, double p1, 
             twx[N / 2 + i] = make_double2((double)cosl(ang), (double)sinl(ang));
         }
     }
-    ok = ok && hipMalloc(&h->d_tw, sizeof(double2) * twx.size()) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_fo, sizeof(double2) * (size_t)h->R * N) == hipSuccess;
-    for (double*& p : h->d_hist) {
-        ok = ok && hipMalloc(&p, 2 * sizeof(double) * (N - 1)) == hipSuccess;
+    ok = ok && h->d_tw.reserve(twx.size()) == HZ_OK;
+    ok = ok && h->d_fo.reserve(2 * (size_t)h->R * N) == HZ_OK;
+    for (hz::DevBuf<double>& p : h->d_hist) {
+        ok = ok && p.reserve(2 * (size_t)(N - 1)) == HZ_OK;
         ok = ok && hipMemset(p, 0, 2 * sizeof(double) * (N - 1)) == hipSuccess;
     }
     ok = ok && hipMemcpy(h->d_win, win.data(), sizeof(double) * N, hipMemcpyHostToDevice) == hipSuccess;
@@ -1518,8 +1507,6 @@ int hz_stft_create(int N, int laps, int window, int proc, double p0, double p1, 
     if (!ok) {
         hz::set_error("hz_stft_create: device allocation failed");
         if (h->stream) (void)hipStreamDestroy(h->stream);
-        for (void* p : {(void*)h->d_win, (void*)h->d_tw, (void*)h->d_fo, (void*)h->d_hist[0], (void*)h->d_hist[1]})
-            if (p) (void)hipFree(p);
         delete h;
         return HZ_E_ALLOC;
     }
@@ -1548,9 +1535,6 @@ int hz_stft_destroy(hz_stft* h) {
     if (!h) return HZ_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void* p : {(void*)h->d_win, (void*)h->d_tw, (void*)h->d_fo, (void*)h->d_hist[0], (void*)h->d_hist[1],
-                    (void*)h->d_spec, (void*)h->d_in, (void*)h->d_out, (void*)h->d_slot})
-        if (p) (void)hipFree(p);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -1589,15 +1573,8 @@ int hz_stft_process_block(hz_stft* h, const double* re, const double* im, double
     HZ_TRY(stft_check(h));
     if (n == 0) return HZ_OK;
     if (!re || !out_re) return HZ_E_INVALID;
-    const size_t bytes = sizeof(double) * n * 2;
-    if (bytes > h->io_cap) {
-        for (double** p : {&h->d_in, &h->d_out})
-            if (*p) HZ_TRY_HIP(hipFree(*p));
-        h->d_in = h->d_out = nullptr;
-        HZ_TRY_HIP(hipMalloc(&h->d_in, bytes));
-        HZ_TRY_HIP(hipMalloc(&h->d_out, bytes));
-        h->io_cap = bytes;
-    }
+    HZ_TRY(h->d_in.reserve(2 * n));
+    HZ_TRY(h->d_out.reserve(2 * n));
     HZ_TRY_HIP(hipMemcpyAsync(h->d_in, re, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
     if (im) HZ_TRY_HIP(hipMemcpyAsync(h->d_in + n, im, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
     HZ_TRY(hz_stft_process_block_device(h, h->d_in, im ? h->d_in + n : nullptr, h->d_out, out_im ? h->d_out + n : nullptr,
@@ -1629,7 +1606,7 @@ int slot_enter(hz_stft* h) {
     h->s_reading.assign(S, 0);
     h->s_writing.assign(S, 1);
     for (int i = 0; i < S; ++i) h->s_wp[i] = -h->stride * i;   // fourier.h:76-77
-    if (!h->d_slot) HZ_TRY_HIP(hipMalloc(&h->d_slot, sizeof(double2) * 2 * (size_t)N));
+    HZ_TRY(h->d_slot.reserve(2 * (size_t)N));
     h->slot_mode = true;
     return HZ_OK;
 }
@@ -1862,9 +1839,9 @@ int hz_stft_profile_read(hz_stft* h, double* frame_ms, double* ola_ms, long* blo
 // ---------------------------------------------------------------------------
 struct hz_dct {
     int N = 0, lg = 0, device = 0;
-    double *h_in = nullptr, *h_out = nullptr;   // pinned, owned (fourier.h:201-207)
-    double *d_a = nullptr, *d_b = nullptr;
-    double2 *d_tw = nullptr, *d_rot = nullptr;
+    hz::PinBuf<double> h_in, h_out;   // pinned, owned (fourier.h:201-207)
+    hz::DevBuf<double> d_a, d_b;
+    hz::DevBuf<double2> d_tw, d_rot;
     hipStream_t stream = nullptr;
 };
 
@@ -1906,21 +1883,14 @@ int hz_dct_create(int N, int device, hz_dct** out) {
         rot[k] = make_double2((double)cosl(a), (double)sinl(a));
     }
     bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipHostMalloc(&h->h_in, sizeof(double) * N) == hipSuccess;
-    ok = ok && hipHostMalloc(&h->h_out, sizeof(double) * N) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_a, sizeof(double) * N) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_b, sizeof(double) * N) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_tw, sizeof(double2) * (N / 2)) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_rot, sizeof(double2) * N) == hipSuccess;
+    ok = ok && h->h_in.reserve(N) == HZ_OK && h->h_out.reserve(N) == HZ_OK;
+    ok = ok && h->d_a.reserve(N) == HZ_OK && h->d_b.reserve(N) == HZ_OK;
+    ok = ok && h->d_tw.reserve(N / 2) == HZ_OK && h->d_rot.reserve(N) == HZ_OK;
     ok = ok && hipMemcpy(h->d_tw, tw.data(), sizeof(double2) * (N / 2), hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && hipMemcpy(h->d_rot, rot.data(), sizeof(double2) * N, hipMemcpyHostToDevice) == hipSuccess;
     if (!ok) {
         hz::set_error("hz_dct_create: allocation failed");
         if (h->stream) (void)hipStreamDestroy(h->stream);
-        for (double* p : {h->h_in, h->h_out})
-            if (p) (void)hipHostFree(p);
-        for (void* p : {(void*)h->d_a, (void*)h->d_b, (void*)h->d_tw, (void*)h->d_rot})
-            if (p) (void)hipFree(p);
         delete h;
         return HZ_E_ALLOC;
     }
@@ -1934,10 +1904,6 @@ int hz_dct_destroy(hz_dct* h) {
     if (!h) return HZ_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (double* p : {h->h_in, h->h_out})
-        if (p) (void)hipHostFree(p);
-    for (void* p : {(void*)h->d_a, (void*)h->d_b, (void*)h->d_tw, (void*)h->d_rot})
-        if (p) (void)hipFree(p);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return HZ_OK;

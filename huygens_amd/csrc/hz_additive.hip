@@ -803,14 +803,21 @@ int hz_add_profile_read(hz_add* h, double* ms, long* launches) {
 
 // ---------------------------------------------------------------------------
 // Sinusoids<double>  (src/sinusoids.h:10-79): one voice, amp = 1, partial i at
-// fundamental (i+1)^harmonicity, weight decay^i / normalization.  The smoothing of
-// fundamental / decay / harmonicity (stiffness relaxation(k), k = 2/SR by default, i.e.
-// 1.5e-8 per sample) is taken to complete at the call boundary.
+// fundamental (i+1)^harmonicity, weight decay^i / normalization.  tick() relaxes fundamental /
+// decay / harmonicity toward their targets with stiffness relaxation(k) (sinusoids.h:46-48) and
+// retargets every synth.  While one of the three still moves, the host steps that recurrence
+// exactly as the reference writes it and renders one sample per launch (operator() before
+// tick(): the sample takes the previous weights, c_first; the tick the new targets); the
+// recurrence reaches its floating-point fixed point after about k SR samples (3 at the default
+// k = 2/SR), and from there on the closed-form block engine is exact.
 // ---------------------------------------------------------------------------
 struct hz_sin {
     PhaseBank bank;
     int O = 0;
     double fundamental = 0, decay = 0, harmonicity = 1;
+    double target_fundamental = 0, target_decay = 0, target_harmonicity = 1;
+    double stiffness = 0;
+    bool moving = true;   // the smoothed parameters may not be at their fixed point yet
 };
 
 namespace {
@@ -822,6 +829,34 @@ void sin_retarget(hz_sin* h) {
         b.ft[i] = h->fundamental * std::pow(i + 1, h->harmonicity);
         b.c[i] = std::pow(h->decay, i) / norm;
     }
+}
+
+// one tick of the smoothed parameters (sinusoids.h:46-48); false once none of them moves
+bool sin_step(hz_sin* h) {
+    const double k = h->stiffness;
+    const double f = h->target_fundamental * (1 - k) + h->fundamental * k;
+    const double d = h->target_decay * (1 - k) + h->decay * k;
+    const double m = h->target_harmonicity * (1 - k) + h->harmonicity * k;
+    if (f == h->fundamental && d == h->decay && m == h->harmonicity) return false;
+    h->fundamental = f;
+    h->decay = d;
+    h->harmonicity = m;
+    sin_retarget(h);
+    return true;
+}
+
+// the first samples of a call, while the parameters still move: one launch each; *done of n rendered
+int sin_transient(hz_sin* h, double* d_dst, long n, long* done) {
+    *done = 0;
+    while (h->moving && *done < n) {
+        if (!sin_step(h)) {
+            h->moving = false;
+            break;
+        }
+        HZ_TRY(h->bank.render(d_dst + *done, 1));
+        ++*done;
+    }
+    return HZ_OK;
 }
 }  // namespace
 
@@ -838,9 +873,10 @@ int hz_sin_create(double fundamental, int overtones, double decay, double harmon
     hz_sin* h = new (std::nothrow) hz_sin();
     if (!h) return HZ_E_ALLOC;
     h->O = overtones;
-    h->fundamental = fundamental;
-    h->decay = decay;
-    h->harmonicity = harmonicity;
+    h->fundamental = h->target_fundamental = fundamental;
+    h->decay = h->target_decay = decay;
+    h->harmonicity = h->target_harmonicity = harmonicity;
+    h->stiffness = hz::relaxation(k);
     // Synth(form, fundamental * pow(i+1, harmonicity)) with the default k = 2/SR (sinusoids.h:23-27)
     int rc = h->bank.init(1, overtones, 0, overtones, hz::relaxation(2.0 / hz::kSR), 0.0, device);
     if (rc != HZ_OK) {
@@ -848,7 +884,6 @@ int hz_sin_create(double fundamental, int overtones, double decay, double harmon
         delete h;
         return rc;
     }
-    (void)k;
     h->bank.act[0] = 1.0;
     h->bank.amp[0] = 1.0;
     h->bank.alive[0] = 1;
@@ -873,8 +908,8 @@ int hz_sin_fundmod(hz_sin* h, double target) {   // sinusoids.h:67-68
     if (!h) return HZ_E_INVALID;
     HZ_TRY_HIP(hipSetDevice(h->bank.device));
     HZ_TRY(h->bank.settle());
-    h->fundamental = target;
-    sin_retarget(h);
+    h->target_fundamental = target;
+    h->moving = true;
     return HZ_OK;
 }
 
@@ -882,8 +917,8 @@ int hz_sin_decaymod(hz_sin* h, double target) {   // sinusoids.h:61-62
     if (!h) return HZ_E_INVALID;
     HZ_TRY_HIP(hipSetDevice(h->bank.device));
     HZ_TRY(h->bank.settle());
-    h->decay = target;
-    sin_retarget(h);
+    h->target_decay = target;
+    h->moving = true;
     return HZ_OK;
 }
 
@@ -891,8 +926,8 @@ int hz_sin_harmmod(hz_sin* h, double target) {    // sinusoids.h:64-65
     if (!h) return HZ_E_INVALID;
     HZ_TRY_HIP(hipSetDevice(h->bank.device));
     HZ_TRY(h->bank.settle());
-    h->harmonicity = target;
-    sin_retarget(h);
+    h->target_harmonicity = target;
+    h->moving = true;
     return HZ_OK;
 }
 
@@ -901,7 +936,18 @@ int hz_sin_fill(hz_sin* h, double* out, size_t n) {
     if (!h) return HZ_E_INVALID;
     HZ_TRY_HIP(hipSetDevice(h->bank.device));
     if (n && !out) return HZ_E_INVALID;
-    return h->bank.fill_host(out, (long)n);
+    long done = 0;
+    if (h->moving && n) {
+        PhaseBank& b = h->bank;
+        HZ_TRY(b.settle());
+        HZ_TRY(b.d_out.reserve(n));
+        HZ_TRY(sin_transient(h, b.d_out, (long)n, &done));
+        if (done) {
+            HZ_TRY_HIP(hipMemcpyAsync(out, b.d_out, sizeof(double) * done, hipMemcpyDeviceToHost, b.stream));
+            HZ_TRY_HIP(hipStreamSynchronize(b.stream));
+        }
+    }
+    return h->bank.fill_host(out + done, (long)n - done);
 }
 
 int hz_sin_fill_device(hz_sin* h, double* d_out, size_t n) {
@@ -909,7 +955,9 @@ int hz_sin_fill_device(hz_sin* h, double* d_out, size_t n) {
     HZ_TRY_HIP(hipSetDevice(h->bank.device));
     if (n && !d_out) return HZ_E_INVALID;
     HZ_TRY(h->bank.settle());
-    return h->bank.render(d_out, (long)n);
+    long done = 0;
+    HZ_TRY(sin_transient(h, d_out, (long)n, &done));
+    return h->bank.render(d_out + done, (long)n - done);
 }
 
 }  // extern "C"

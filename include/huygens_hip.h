@@ -318,7 +318,9 @@ int hz_sin_destroy(hz_sin* h);
 int hz_sin_fundmod(hz_sin* h, double target);    /* 67-68 */
 int hz_sin_decaymod(hz_sin* h, double target);   /* 61-62 */
 int hz_sin_harmmod(hz_sin* h, double target);    /* 64-65 */
-/* n x { out[t] = operator()(); tick(); }  34-57 */
+/* n x { out[t] = operator()(); tick(); }  34-57.  After a modulator call the samples during which
+ * fundamental / decay / harmonicity still relax toward their targets (stiffness relaxation(k): about
+ * k SR samples, 3 at the default k) cost one launch each; the rest of the call is one block. */
 int hz_sin_fill(hz_sin* h, double* out, size_t n);
 int hz_sin_fill_device(hz_sin* h, double* d_out, size_t n);
 

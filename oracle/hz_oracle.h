@@ -5,14 +5,16 @@
  * as the parity checker for the HIP kernels in huygens_amd/csrc.  Only tests/,
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg may load it.
  *
- * Parity status: the reference itself cannot be compiled in this image
- * (Eigen >= 3.4, FFTW3, PortAudio and RtMidi headers are absent; see
- * DESIGN.md "Oracle") and its tests hold no golden vectors.  This
- * restatement is therefore pinned against (a) an independent numpy
- * restatement that writes tests/golden/ fixtures, (b) scipy.signal.lfilter /
- * numpy.fft / scipy.fft.dct known-answer checks of the third-party maths
- * (Eigen GEMV, FFTW DFT/REDFT conventions), and (c) closed-form known
- * answers.  Strictly, by the reference's own fixtures: parity unpinned.
+ * Parity status: the classes of the reference that need neither Eigen nor FFTW (Oscillator,
+ * Synth, Sinusoids, Additive/Minimizer, Bowl, Buffer/Delay, Granulator, the wave shapes and
+ * scalar helpers) compile from its own headers (oracle/ref/, `make ref`), and this restatement
+ * reproduces their output bit for bit (tests/test_ref_pinned_cpu.py over tests/golden/ref_*.npz,
+ * tests/test_ref_live_cpu.py against the live binary).  The rest (Filterbank, Oscbank: Eigen;
+ * Fourier, StaticSTFT, Cosine, Freezer: FFTW; headers absent here, see DESIGN.md "Oracle") is
+ * pinned against (a) an independent numpy restatement that writes tests/golden/ fixtures,
+ * (b) scipy.signal.lfilter / numpy.fft / scipy.fft.dct known-answer checks of the third-party
+ * maths (Eigen GEMV, FFTW DFT/REDFT conventions), and (c) closed-form known answers; the
+ * reference's tests hold no golden vectors, so for those classes, strictly: parity unpinned.
  *
  * Constants follow /root/reference/src/includes.h:30-48 (truncated PI,
  * integer SR, relaxation()).
@@ -65,6 +67,18 @@ void     orc_osc_phases(orc_osc* o, double* z /* 2N interleaved */);
 int      orc_osc_active_count(orc_osc* o);
 /* n x { mix[i] = mixdown(); per_band[i][:] = phases; tick(); } (per_band may be NULL) */
 void     orc_osc_fill(orc_osc* o, double* mix /* 2n */, double* per_band /* 2nN */, long n);
+
+/* ---- Oscillator<double> / Synth<double> (src/oscillator.h:12-71, src/synth.h:10-21), the
+ * Wave<double> shapes (src/wave.h:142-150) and dbtoa (src/includes.h:66-69) ---- */
+typedef struct orc_oscl orc_oscl;
+orc_oscl* orc_oscl_create(double f, double phi, double k);
+void      orc_oscl_destroy(orc_oscl* s);
+void      orc_oscl_freqmod(orc_oscl* s, double target);
+void      orc_oscl_phasemod(orc_oscl* s, double offset);
+void      orc_oscl_reset(orc_oscl* s, double f);
+void      orc_oscl_fill(orc_oscl* s, double* phase, double* wave, long n);   /* either may be NULL */
+double    orc_wave(int id, double p);
+double    orc_dbtoa(double db);
 
 /* ---- Additive<double> (src/additive.h:11-71 + src/minimizer.h note API) - */
 typedef struct orc_add orc_add;

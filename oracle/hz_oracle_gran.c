@@ -5,8 +5,9 @@
  * Buffer<double> source (src/buffer.h:9-86) through the FUNCTIONAL hann window
  * (src/wave.h:65-70,148), in the per-sample order of tests/granny.cpp:34-56:
  *   source.write(x); y = granny(); <requests>; source.tick(); granny.tick();
- * Parity: unpinned by the reference's own files (no fixtures or known answers for
- * this class); pinned here by tests/test_granulator_cpu.py's closed-form cases.
+ * Parity: bit-equal to the reference's own Granulator<double>, compiled from its headers
+ * (tests/test_ref_pinned_cpu.py, tests/test_ref_live_cpu.py), beside the closed-form cases of
+ * tests/test_granulator_cpu.py.
  */
 #include <math.h>
 #include <stdlib.h>

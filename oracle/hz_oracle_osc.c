@@ -3,7 +3,8 @@
  * Scalar restatement of Oscillator<T>/Synth<T>, Sinusoids<T> and Additive<T>
  * (+ the Minimizer note API it inherits), op for op.  Physics (Minimizer::physics,
  * src/minimizer.h:61-108) is out of scope and never called, so particle positions stay
- * where request() puts them.  abs() is taken as fabs (macOS libc++).
+ * where request() puts them.  abs() is taken as fabs (macOS libc++; the pin of
+ * oracle/ref/hz_ref_dump.cpp asserts the same overload).
  */
 #include <float.h>
 #include <math.h>
@@ -44,6 +45,66 @@ static void osc_tick(osc_t* o)
     o->phase -= (int)o->phase;
     o->target_phase -= (int)o->target_phase;
 }
+
+/* ---- Oscillator<double> / Synth<double> on their own  src/oscillator.h:12-71, src/synth.h:10-21 */
+struct orc_oscl { osc_t o; };
+
+orc_oscl* orc_oscl_create(double f, double phi, double k)
+{
+    orc_oscl* s = (orc_oscl*)calloc(1, sizeof(orc_oscl));
+    osc_init(&s->o, f, phi, k);
+    return s;
+}
+
+void orc_oscl_destroy(orc_oscl* s) { free(s); }
+
+void orc_oscl_freqmod(orc_oscl* s, double target) { s->o.target_freq = target; } /* oscillator.h:46-47 */
+
+/* oscillator.h:49-56 */
+void orc_oscl_phasemod(orc_oscl* s, double offset)
+{
+    s->o.target_phase += offset;
+    s->o.target_phase -= (int)s->o.target_phase;
+    s->o.target_phase += 1;
+    s->o.target_phase -= (int)s->o.target_phase;
+}
+
+/* oscillator.h:58-62 */
+void orc_oscl_reset(orc_oscl* s, double f)
+{
+    s->o.frequency = s->o.target_freq = f;
+    s->o.phase = s->o.target_phase = 0;
+}
+
+/* n x { phase[t] = Oscillator::operator()(); wave[t] = Synth(&cycle)::operator()(); tick(); } */
+void orc_oscl_fill(orc_oscl* s, double* phase, double* wave, long n)
+{
+    for (long t = 0; t < n; t++) {
+        if (phase) phase[t] = s->o.phase;
+        if (wave) wave[t] = cycle(s->o.phase);
+        osc_tick(&s->o);
+    }
+}
+
+/* ---- the Wave<double> shapes of src/wave.h:142-150 (FUNCTIONAL lookup: shape(input)) ----
+ * id: 0 saw, 1 triangle, 2 square, 3 phasor, 4 cycle, 5 hann, 6 halfhann, 7 limiter */
+double orc_wave(int id, double p)
+{
+    switch (id) {
+    case 0: return 2 * p - 1;
+    case 1: return fabs(fmod(4 * p + 3, 4.0) - 2) - 1;
+    case 2: return p > 0.5 ? 1 : (p < 0.5 ? -1 : 0);
+    case 3: return p;
+    case 4: return cycle(p);
+    case 5: return 0.5 * (1 - cos(2 * ORC_PI * p));
+    case 6: return sqrt(0.5 * (1 - cos(2 * ORC_PI * p)));
+    case 7: return 2.0 / ORC_PI * atan(p);
+    }
+    return 0;
+}
+
+/* src/includes.h:66-69 */
+double orc_dbtoa(double db) { return pow(10, db / 20); }
 
 /* ---- Additive<double>  src/additive.h:11-71, src/minimizer.h:23-206 ------- */
 struct orc_add {

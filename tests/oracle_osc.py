@@ -22,7 +22,52 @@ _SIGS = {
     "orc_sin_decaymod": (None, [VP, D]),
     "orc_sin_harmmod": (None, [VP, D]),
     "orc_sin_fill": (None, [VP, PD, L]),
+    "orc_oscl_create": (VP, [D, D, D]),
+    "orc_oscl_destroy": (None, [VP]),
+    "orc_oscl_freqmod": (None, [VP, D]),
+    "orc_oscl_phasemod": (None, [VP, D]),
+    "orc_oscl_reset": (None, [VP, D]),
+    "orc_oscl_fill": (None, [VP, PD, PD, L]),
+    "orc_wave": (D, [I, D]),
+    "orc_dbtoa": (D, [D]),
 }
+
+
+class OracleOscillator:
+    """Oscillator<double>(f, phi, k); wave=True: Synth<double>(&cycle, f, phi, k)."""
+
+    def __init__(self, f=0.0, phi=0.0, k=2.0 / 48000, wave=False):
+        self.l = _bind(_SIGS)
+        self.h = self.l.orc_oscl_create(f, phi, k)
+        self.wave = wave
+
+    def __del__(self):
+        try:
+            self.l.orc_oscl_destroy(self.h)
+        except Exception:
+            pass
+
+    def freqmod(self, v):
+        self.l.orc_oscl_freqmod(self.h, v)
+
+    def phasemod(self, v):
+        self.l.orc_oscl_phasemod(self.h, v)
+
+    def reset(self, v):
+        self.l.orc_oscl_reset(self.h, v)
+
+    def fill(self, n):
+        out = np.zeros(n)
+        self.l.orc_oscl_fill(self.h, None if self.wave else _p(out), _p(out) if self.wave else None, n)
+        return out
+
+
+def oracle_wave(wave_id, p):
+    return _bind(_SIGS).orc_wave(wave_id, p)
+
+
+def oracle_dbtoa(db):
+    return _bind(_SIGS).orc_dbtoa(db)
 
 
 class OracleAdditive:
@@ -111,4 +156,10 @@ def run_note_events(obj, g):
                 obj.decaymod(float(ea[e]))
             elif k == 12:
                 obj.harmmod(float(ea[e]))
+            elif k == 20:
+                obj.freqmod(float(ea[e]))
+            elif k == 21:
+                obj.phasemod(float(ea[e]))
+            elif k == 22:
+                obj.reset(float(ea[e]))
     return out

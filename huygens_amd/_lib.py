@@ -37,6 +37,9 @@ HZ_DIST_SOFTCLIP = 1
 HZ_DIST_SATURATE = 2
 HZ_DIST_LIMITER = 3
 
+HZ_GRAV_TRUNC = 1
+HZ_GRAV_FABS = 2
+
 _ERRNAMES = {
     HZ_E_INVALID: "HZ_E_INVALID", HZ_E_RANGE: "HZ_E_RANGE", HZ_E_HIP: "HZ_E_HIP",
     HZ_E_NODEV: "HZ_E_NODEV", HZ_E_ALLOC: "HZ_E_ALLOC", HZ_E_UNSUPPORTED: "HZ_E_UNSUPPORTED",
@@ -155,6 +158,12 @@ _SIGS = {
     "hz_add_set_target_groups": (I, [VP, I]),
     "hz_add_profile": (I, [VP, I]),
     "hz_add_profile_read": (I, [VP, PD, C.POINTER(L)]),
+    "hz_add_physics_every": (I, [VP, I, I]),
+    "hz_add_physics": (I, [VP, I]),
+    "hz_add_peek": (I, [VP, PD]),
+    "hz_add_positions": (I, [VP, PD]),
+    "hz_add_tune_physics": (I, [VP, I, I]),
+    "hz_add_physics_profile_read": (I, [VP, PD, PD]),
     "hz_sin_create": (I, [D, I, D, D, D, I, C.POINTER(VP)]),
     "hz_sin_destroy": (I, [VP]),
     "hz_sin_fundmod": (I, [VP, D]),

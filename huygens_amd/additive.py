@@ -1,9 +1,9 @@
 """Additive<double> and Sinusoids<double> over the HIP engine.
 
 Mirrors soundmath::Additive<T> (src/additive.h:11-71, note API from
-src/minimizer.h:111-187; physics() is out of scope) and soundmath::Sinusoids<T>
-(src/sinusoids.h:10-79), waveform cycle = sin(2 PI p).  fill(n) ==
-n x {out[t] = operator()(); tick();} on the GPU.
+src/minimizer.h:111-187, and Minimizer::physics(), src/minimizer.h:61-108, through
+physics_every / physics) and soundmath::Sinusoids<T> (src/sinusoids.h:10-79), waveform
+cycle = sin(2 PI p).  fill(n) == n x {out[t] = operator()(); tick();} on the GPU.
 """
 from __future__ import annotations
 
@@ -11,7 +11,11 @@ import ctypes as C
 
 import numpy as np
 
+from ._lib import HZ_GRAV_FABS as GRAV_FABS
+from ._lib import HZ_GRAV_TRUNC as GRAV_TRUNC
 from ._lib import check, dptr, load
+
+__all__ = ["Additive", "Sinusoids", "GRAV_TRUNC", "GRAV_FABS", "lookahead_info"]
 
 
 class Additive:
@@ -25,6 +29,7 @@ class Additive:
             check(lib.hz_add_create_shard(voices, overtones, shard[0], shard[1], decay, harmonicity, k, device,
                                           C.byref(h)))
         self._h, self._lib = h, lib
+        self._shape = (voices, overtones)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -75,6 +80,37 @@ class Additive:
         ms, c = C.c_double(), C.c_long()
         check(self._lib.hz_add_profile_read(self._h, C.byref(ms), C.byref(c)))
         return ms.value, c.value
+
+    # ---- Minimizer::physics() (src/minimizer.h:61-108); `law` is GRAV_TRUNC or GRAV_FABS, no default
+    def physics_every(self, period: int, law: int):
+        """fill(n) becomes n x {out = operator()(); if (T >= period and T % period == 0) physics();
+        tick(); T++}, T counted from this call; period 0 switches physics off."""
+        check(self._lib.hz_add_physics_every(self._h, period, law))
+
+    def physics(self, law: int):
+        """One physics() step now; the next tick reads the moved positions."""
+        check(self._lib.hz_add_physics(self._h, law))
+
+    def peek(self) -> float:
+        """operator()() without tick()."""
+        y = C.c_double()
+        check(self._lib.hz_add_peek(self._h, C.byref(y)))
+        return y.value
+
+    def positions(self) -> np.ndarray:
+        """particles[v * overtones + j]() for every particle, [voices * overtones]."""
+        out = np.zeros(self._shape[0] * self._shape[1])
+        check(self._lib.hz_add_positions(self._h, dptr(out)))
+        return out
+
+    def tune_physics(self, single_group_max: int = 0, tile: int = 0):
+        check(self._lib.hz_add_tune_physics(self._h, single_group_max, tile))
+
+    def physics_profile_read(self):
+        """(physics kernels ms, audio kernels ms) of the physics path since profile(True)."""
+        p, a = C.c_double(), C.c_double()
+        check(self._lib.hz_add_physics_profile_read(self._h, C.byref(p), C.byref(a)))
+        return p.value, a.value
 
 
 class Sinusoids:

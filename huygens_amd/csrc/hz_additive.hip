@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "hz_common.h"
+#include "hz_minimizer.h"
 
 namespace {
 
@@ -590,7 +591,28 @@ struct hz_add {
     std::vector<double> active;     // Minimizer::active (amplitude targets)
     std::vector<double> pitches;    // Minimizer::pitches
     std::vector<double> guide;      // guides[v].position
-    std::vector<double> position;   // particles[v*O+j].position (all overtones)
+    std::vector<double> position;   // particles[v*O+j].position (all overtones); with physics on, the
+                                    // device copy (phys.d_x) is the one that moves
+    std::vector<double> equilibrium;   // springs[v*O+j].equilibrium
+    // Minimizer::physics() (hz_minimizer.hip).  The device state exists from the first physics call
+    // on; before it no particle has moved (velocity 0) and the host mirrors above are complete.
+    struct Physics {
+        enum { OFF, MANUAL, PERIODIC };
+        int mode = OFF;          // MANUAL: hz_add_physics() steps, PERIODIC: hz_add_physics_every(period > 0)
+        int law = 0, period = 0;
+        long T = 0;              // samples since the period was set
+        bool ready = false;
+        int single_max = kSingleMax, tile = kStepTile;
+        static constexpr int kSingleLimit = 1024, kSingleMax = 256, kStepTile = 256;
+        // a call is rendered in pieces of at most kMaxSamples samples whose position rows
+        // ([steps + 1][V O] doubles) fit kMaxRowBytes
+        static constexpr long kMaxSamples = 4096;
+        static constexpr size_t kMaxRowBytes = (size_t)32 << 20;
+        hz::DevBuf<double> d_x, d_v, d_eq, d_guide, d_c, d_rows, d_amp, d_partial;
+        std::vector<double> amp;   // [n + 1][V] envelope rows of the piece being rendered
+        std::vector<hipEvent_t> ev;   // profile: 3 per piece (start, physics done, audio done)
+        size_t ev_used = 0;
+    } phys;
 };
 
 namespace {
@@ -612,6 +634,181 @@ void add_retarget(hz_add* h, int v) {
         const int j = b.o0 + jl;
         b.ft[(size_t)v * b.OL + jl] = (double)mtofl((long double)h->position[(size_t)v * h->O + j]);
     }
+}
+
+// ---- Minimizer::physics() (kernels in hz_minimizer.hip) ----------------------------------
+
+int phys_law_check(hz_add* h, int law) {
+    if (!h) {
+        hz::set_error("null hz_add handle");
+        return HZ_E_INVALID;
+    }
+    if (law != HZ_GRAV_TRUNC && law != HZ_GRAV_FABS) {
+        hz::set_error("gravity law %d: HZ_GRAV_TRUNC or HZ_GRAV_FABS (there is no default)", law);
+        return HZ_E_INVALID;
+    }
+    if (h->bank.OL != h->O) {
+        hz::set_error("physics on an overtone shard: every partial is needed");
+        return HZ_E_UNSUPPORTED;
+    }
+    return HZ_OK;
+}
+
+hz::MinParams phys_params(const hz_add* h) {
+    hz::MinParams p;
+    p.V = h->V;
+    p.O = h->O;
+    p.G = 1 * 50000;          // includes.h:34 FORCE; minimizer.h:56
+    p.eps = 0.0001;           // particle.h:108
+    p.k0 = 0.1 * 50000;       // minimizer.h:40
+    p.k1 = 1 * 50000;         // minimizer.h:45
+    p.drag = hz::relaxation(0.01);   // particle.h:23-27
+    return p;
+}
+
+// device rows of one voice after request(): position, equilibrium, velocity 0
+int phys_upload_voice(hz_add* h, int v) {
+    hz_add::Physics& ph = h->phys;
+    const size_t O = h->O, at = (size_t)v * O;
+    hipStream_t st = h->bank.stream;
+    HZ_TRY_HIP(hipMemcpyAsync(ph.d_x + at, &h->position[at], sizeof(double) * O, hipMemcpyHostToDevice, st));
+    HZ_TRY_HIP(hipMemcpyAsync(ph.d_eq + at, &h->equilibrium[at], sizeof(double) * O, hipMemcpyHostToDevice, st));
+    HZ_TRY_HIP(hipMemsetAsync(ph.d_v + at, 0, sizeof(double) * O, st));
+    HZ_TRY_HIP(hipStreamSynchronize(st));   // pageable sources
+    return HZ_OK;
+}
+
+// the device state, from the host mirrors (nothing has moved before the first physics call)
+int phys_ensure(hz_add* h) {
+    hz_add::Physics& ph = h->phys;
+    if (ph.ready) return HZ_OK;
+    const size_t P = (size_t)h->V * h->O;
+    hipStream_t st = h->bank.stream;
+    HZ_TRY(ph.d_x.reserve(P));
+    HZ_TRY(ph.d_v.reserve(P));
+    HZ_TRY(ph.d_eq.reserve(P));
+    HZ_TRY(ph.d_c.reserve(P));
+    HZ_TRY(ph.d_guide.reserve(h->V));
+    HZ_TRY_HIP(hipMemcpyAsync(ph.d_x, h->position.data(), sizeof(double) * P, hipMemcpyHostToDevice, st));
+    HZ_TRY_HIP(hipMemcpyAsync(ph.d_eq, h->equilibrium.data(), sizeof(double) * P, hipMemcpyHostToDevice, st));
+    HZ_TRY_HIP(hipMemcpyAsync(ph.d_c, h->bank.c.data(), sizeof(double) * P, hipMemcpyHostToDevice, st));
+    HZ_TRY_HIP(hipMemsetAsync(ph.d_v, 0, sizeof(double) * P, st));
+    HZ_TRY_HIP(hipStreamSynchronize(st));
+    ph.ready = true;
+    return HZ_OK;
+}
+
+// `steps` physics steps on the device state: rows[0] <- x, kernels write rows 1..steps, x <- rows[steps]
+int phys_steps(hz_add* h, int steps) {
+    hz_add::Physics& ph = h->phys;
+    const size_t P = (size_t)h->V * h->O;
+    hipStream_t st = h->bank.stream;
+    HZ_TRY(ph.d_rows.reserve((size_t)(steps + 1) * P));
+    HZ_TRY_HIP(hipMemcpyAsync(ph.d_rows, ph.d_x, sizeof(double) * P, hipMemcpyDeviceToDevice, st));
+    if (steps <= 0) return HZ_OK;
+    HZ_TRY(hz::min_run(st, phys_params(h), ph.law, steps, (long)P <= ph.single_max, ph.tile, ph.d_rows, ph.d_v,
+                       ph.d_eq, h->bank.d_act, ph.d_guide));
+    HZ_TRY_HIP(hipMemcpyAsync(ph.d_x, ph.d_rows + (size_t)steps * P, sizeof(double) * P, hipMemcpyDeviceToDevice, st));
+    return HZ_OK;
+}
+
+// envelope rows of n samples, op for op (additive.h:40-41): row 0 = amplitudes now, row t + 1 after
+// sample t's tick
+void phys_envelope(const PhaseBank& b, long n, std::vector<double>& rows) {
+#pragma clang fp contract(off)
+    const int V = b.V;
+    rows.resize((size_t)(n + 1) * V);
+    for (int v = 0; v < V; ++v) rows[v] = b.amp[v];
+    for (long t = 0; t < n; ++t)
+        for (int v = 0; v < V; ++v)
+            rows[(size_t)(t + 1) * V + v] = (1 - b.a) * b.act[v] + b.a * rows[(size_t)t * V + v];
+}
+
+// active / guide / envelope rows to the device (pageable sources: synchronised)
+int phys_upload_call(hz_add* h, long n_rows) {
+    hz_add::Physics& ph = h->phys;
+    PhaseBank& b = h->bank;
+    HZ_TRY(ph.d_amp.reserve((size_t)n_rows * b.V));
+    HZ_TRY_HIP(hipMemcpyAsync(ph.d_amp, ph.amp.data(), sizeof(double) * n_rows * b.V, hipMemcpyHostToDevice, b.stream));
+    HZ_TRY_HIP(hipMemcpyAsync(b.d_act, b.act.data(), sizeof(double) * b.V, hipMemcpyHostToDevice, b.stream));
+    HZ_TRY_HIP(hipMemcpyAsync(ph.d_guide, h->guide.data(), sizeof(double) * b.V, hipMemcpyHostToDevice, b.stream));
+    HZ_TRY_HIP(hipStreamSynchronize(b.stream));
+    return HZ_OK;
+}
+
+// the audio of n samples over position rows already on the device; d_dst [n]
+int phys_audio(hz_add* h, double* d_dst, long n, const double* rows, int period, long T0, int advance) {
+    hz_add::Physics& ph = h->phys;
+    PhaseBank& b = h->bank;
+    const int P = h->V * h->O, G = hz::add_track_groups(P);
+    HZ_TRY(ph.d_partial.reserve((size_t)G * n));
+    hz::TrackArgs a;
+    a.rows = rows;
+    a.amp = ph.d_amp;
+    a.act = b.d_act;
+    a.c = ph.d_c;
+    a.phi = b.d_phi;
+    a.f = b.d_f;
+    a.partial = ph.d_partial;
+    a.n = n;
+    a.n_pad = n;
+    a.T0 = T0;
+    a.period = period;
+    a.P = P;
+    a.V = h->V;
+    a.O = h->O;
+    a.s = b.s;
+    a.advance = advance;
+    HZ_TRY(hz::add_track(b.stream, a));
+    hipLaunchKernelGGL(add_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, b.stream,
+                       (const double*)ph.d_partial, n, G, n, b.scale, d_dst);
+    HZ_TRY_HIP(hipGetLastError());
+    return HZ_OK;
+}
+
+// n x { out[t] = operator()(); if (T >= period && T % period == 0) physics(); tick(); T++; } into
+// d_dst (device), in pieces whose position rows stay within Physics::kMaxRowBytes
+int phys_render(hz_add* h, double* d_dst, long n) {
+    hz_add::Physics& ph = h->phys;
+    PhaseBank& b = h->bank;
+    if (n <= 0) return HZ_OK;
+    HZ_TRY(b.settle());
+    HZ_TRY(phys_ensure(h));
+    const size_t P = (size_t)h->V * h->O;
+    const int period = ph.mode == hz_add::Physics::PERIODIC ? ph.period : 0;
+    const long max_steps = std::max<long>(1, (long)(hz_add::Physics::kMaxRowBytes / (sizeof(double) * P)) - 1);
+    for (long done = 0; done < n;) {
+        long m = std::min(n - done, hz_add::Physics::kMaxSamples);
+        if (period > 0) m = std::min(m, max_steps * period);
+        int steps = 0;
+        for (long t = 0; t < m && period > 0; ++t)
+            steps += (ph.T + t >= period && (ph.T + t) % period == 0) ? 1 : 0;
+        phys_envelope(b, m, ph.amp);
+        HZ_TRY(phys_upload_call(h, m + 1));
+        hipEvent_t* e = nullptr;
+        if (b.prof) {
+            if (ph.ev_used + 3 > ph.ev.size())
+                for (int q = 0; q < 96; ++q) {
+                    hipEvent_t ne;
+                    HZ_TRY_HIP(hz::prof_event_create(&ne));
+                    ph.ev.push_back(ne);
+                }
+            e = &ph.ev[ph.ev_used];
+            ph.ev_used += 3;
+            HZ_TRY_HIP(hipEventRecord(e[0], b.stream));
+        }
+        HZ_TRY(phys_steps(h, steps));
+        if (e) HZ_TRY_HIP(hipEventRecord(e[1], b.stream));
+        HZ_TRY(phys_audio(h, d_dst + done, m, ph.d_rows, period, ph.T, 1));
+        if (e) HZ_TRY_HIP(hipEventRecord(e[2], b.stream));
+        for (int v = 0; v < b.V; ++v) {
+            b.amp[v] = ph.amp[(size_t)m * b.V + v];
+            if (b.act[v] != 0.0 || b.amp[v] != 0.0) b.alive[v] = 1;
+        }
+        if (period > 0) ph.T += m;
+        done += m;
+    }
+    return HZ_OK;
 }
 
 }  // namespace
@@ -649,6 +846,7 @@ int hz_add_create_shard(int voices, int overtones, int o_begin, int o_count, dou
     h->pitches.assign(voices, 0.0);
     h->guide.assign(voices, 0.0);
     h->position.assign((size_t)voices * overtones, 0.0);
+    h->equilibrium.assign((size_t)voices * overtones, 0.0);
     *out = h;
     return HZ_OK;
 }
@@ -660,12 +858,13 @@ int hz_add_create(int voices, int overtones, double decay, double harmonicity, d
 int hz_add_destroy(hz_add* h) {
     if (!h) return HZ_OK;
     h->bank.release();
+    for (hipEvent_t e : h->phys.ev) (void)hipEventDestroy(e);
     delete h;
     return HZ_OK;
 }
 
-// request(fundamental, amplitude)  minimizer.h:111-158; physics is out of scope, so the
-// particle positions stay where request() puts them.
+// request(fundamental, amplitude)  minimizer.h:111-158: the voice's particles (mass 1, v = a = 0) and
+// spring equilibria are re-initialised; with physics on, on the device too.
 int hz_add_request(hz_add* h, double fundamental, double amplitude, int* voice_out) {
     if (!h) return HZ_E_INVALID;
     HZ_TRY(add_check(h));
@@ -692,13 +891,17 @@ int hz_add_request(hz_add* h, double fundamental, double amplitude, int* voice_o
     }
     h->active[voice] = amplitude;
     h->guide[voice] = 69 + std::log2(fundamental / 440.0) * 12;
+    double frequency = fundamental;
     for (int j = 0; j < h->O; ++j) {
-        const double frequency =
-            fundamental * (1 + std::pow((double)j / (h->O - 1), h->harmonicity) * (h->O - 1));
-        h->position[(size_t)voice * h->O + j] = 69 + std::log2(frequency / 440.0) * 12;
+        const double previous = frequency;
+        frequency = fundamental * (1 + std::pow((double)j / (h->O - 1), h->harmonicity) * (h->O - 1));
+        const double pitch = 69 + std::log2(frequency / 440.0) * 12;
+        h->position[(size_t)voice * h->O + j] = pitch;
+        h->equilibrium[(size_t)voice * h->O + j] = pitch - (69 + std::log2(previous / 440.0) * 12);
     }
     h->bank.act[voice] = amplitude;
     add_retarget(h, voice);
+    if (h->phys.ready) HZ_TRY(phys_upload_voice(h, voice));   // particles re-initialised: v = 0
     if (voice_out) *voice_out = voice;
     return HZ_OK;
 }
@@ -736,12 +939,22 @@ int hz_add_endnote(hz_add* h, double pitch) {   // minimizer.h:182-187
 int hz_add_fill(hz_add* h, double* out, size_t n) {
     HZ_TRY(add_check(h));
     if (n && !out) return HZ_E_INVALID;
+    if (h->phys.mode != hz_add::Physics::OFF) {   // served directly, whatever the length
+        if (!n) return HZ_OK;
+        PhaseBank& b = h->bank;
+        HZ_TRY(b.d_out.reserve(n));
+        HZ_TRY(phys_render(h, b.d_out, (long)n));
+        HZ_TRY_HIP(hipMemcpyAsync(out, b.d_out, sizeof(double) * n, hipMemcpyDeviceToHost, b.stream));
+        HZ_TRY_HIP(hipStreamSynchronize(b.stream));
+        return HZ_OK;
+    }
     return h->bank.fill_host(out, (long)n);
 }
 
 int hz_add_fill_device(hz_add* h, double* d_out, size_t n) {
     HZ_TRY(add_check(h));
     if (n && !d_out) return HZ_E_INVALID;
+    if (h->phys.mode != hz_add::Physics::OFF) return phys_render(h, d_out, (long)n);
     HZ_TRY(h->bank.settle());
     return h->bank.render(d_out, (long)n);
 }
@@ -782,6 +995,7 @@ int hz_add_profile(hz_add* h, int enable) {
     h->bank.prof = enable != 0;
     h->bank.ev_used = 0;
     h->bank.launches = 0;
+    h->phys.ev_used = 0;
     return HZ_OK;
 }
 
@@ -796,6 +1010,110 @@ int hz_add_profile_read(hz_add* h, double* ms, long* launches) {
     }
     if (ms) *ms = m;
     if (launches) *launches = h->bank.launches;
+    return HZ_OK;
+}
+
+int hz_add_physics_every(hz_add* h, int period, int law) {
+    HZ_TRY(phys_law_check(h, law));
+    if (period < 0) {
+        hz::set_error("hz_add_physics_every: period %d", period);
+        return HZ_E_INVALID;
+    }
+    HZ_TRY(add_check(h));
+    HZ_TRY(h->bank.settle());
+    hz_add::Physics& ph = h->phys;
+    if (period > 0) {
+        HZ_TRY(phys_ensure(h));
+        ph.mode = hz_add::Physics::PERIODIC;
+        ph.law = law;
+        ph.period = period;
+        ph.T = 0;
+        return HZ_OK;
+    }
+    if (ph.mode != hz_add::Physics::OFF) {   // the static engine renders from the positions as moved
+        const size_t P = (size_t)h->V * h->O;
+        HZ_TRY_HIP(hipMemcpyAsync(h->position.data(), ph.d_x, sizeof(double) * P, hipMemcpyDeviceToHost,
+                                  h->bank.stream));
+        HZ_TRY_HIP(hipStreamSynchronize(h->bank.stream));
+        for (int v = 0; v < h->V; ++v) add_retarget(h, v);
+    }
+    ph.mode = hz_add::Physics::OFF;
+    ph.period = 0;
+    return HZ_OK;
+}
+
+int hz_add_physics(hz_add* h, int law) {
+    HZ_TRY(phys_law_check(h, law));
+    HZ_TRY(add_check(h));
+    HZ_TRY(h->bank.settle());
+    HZ_TRY(phys_ensure(h));
+    hz_add::Physics& ph = h->phys;
+    if (ph.mode == hz_add::Physics::OFF) ph.mode = hz_add::Physics::MANUAL;
+    ph.law = law;
+    ph.amp.assign(h->bank.amp.begin(), h->bank.amp.end());
+    HZ_TRY(phys_upload_call(h, 1));   // active and guides
+    return phys_steps(h, 1);
+}
+
+int hz_add_peek(hz_add* h, double* y) {
+    HZ_TRY(add_check(h));
+    if (!y) return HZ_E_INVALID;
+    if (h->bank.OL != h->O) {
+        hz::set_error("hz_add_peek on an overtone shard");
+        return HZ_E_UNSUPPORTED;
+    }
+    PhaseBank& b = h->bank;
+    HZ_TRY(b.settle());
+    HZ_TRY(phys_ensure(h));
+    // the per-sample path: the ticks that follow are served directly, not from a speculative block
+    if (h->phys.mode == hz_add::Physics::OFF) h->phys.mode = hz_add::Physics::MANUAL;
+    phys_envelope(b, 1, h->phys.amp);
+    HZ_TRY(phys_upload_call(h, 2));
+    HZ_TRY(b.d_out.reserve(1));
+    HZ_TRY(phys_audio(h, b.d_out, 1, h->phys.d_x, 0, 0, 0));
+    HZ_TRY_HIP(hipMemcpyAsync(y, b.d_out, sizeof(double), hipMemcpyDeviceToHost, b.stream));
+    HZ_TRY_HIP(hipStreamSynchronize(b.stream));
+    return HZ_OK;
+}
+
+int hz_add_positions(hz_add* h, double* out) {
+    HZ_TRY(add_check(h));
+    if (!out) return HZ_E_INVALID;
+    const size_t P = (size_t)h->V * h->O;
+    if (!h->phys.ready) {   // nothing has moved yet
+        std::memcpy(out, h->position.data(), sizeof(double) * P);
+        return HZ_OK;
+    }
+    HZ_TRY_HIP(hipMemcpyAsync(out, h->phys.d_x, sizeof(double) * P, hipMemcpyDeviceToHost, h->bank.stream));
+    HZ_TRY_HIP(hipStreamSynchronize(h->bank.stream));
+    return HZ_OK;
+}
+
+int hz_add_tune_physics(hz_add* h, int single_group_max, int tile) {
+    if (!h || single_group_max < 0 || single_group_max > hz_add::Physics::kSingleLimit || tile < 0 || tile > 1024 ||
+        tile % 64 != 0) {
+        hz::set_error("hz_add_tune_physics: single_group_max in [0, 1024], tile a multiple of 64 up to 1024");
+        return HZ_E_INVALID;
+    }
+    // (a request of 0 particles for the single-workgroup path cannot be told from "default": 1 does it)
+    h->phys.single_max = single_group_max ? single_group_max : hz_add::Physics::kSingleMax;
+    h->phys.tile = tile ? tile : hz_add::Physics::kStepTile;
+    return HZ_OK;
+}
+
+int hz_add_physics_profile_read(hz_add* h, double* physics_ms, double* audio_ms) {
+    HZ_TRY(add_check(h));
+    HZ_TRY_HIP(hipStreamSynchronize(h->bank.stream));
+    double p = 0, a = 0;
+    for (size_t i = 0; i + 3 <= h->phys.ev_used; i += 3) {
+        float x = 0;
+        HZ_TRY_HIP(hipEventElapsedTime(&x, h->phys.ev[i], h->phys.ev[i + 1]));
+        p += x;
+        HZ_TRY_HIP(hipEventElapsedTime(&x, h->phys.ev[i + 1], h->phys.ev[i + 2]));
+        a += x;
+    }
+    if (physics_ms) *physics_ms = p;
+    if (audio_ms) *audio_ms = a;
     return HZ_OK;
 }
 

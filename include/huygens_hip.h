@@ -279,7 +279,7 @@ int hz_osc_profile(hz_osc* h, int enable);
 int hz_osc_profile_read(hz_osc* h, double* ms, long* launches);
 
 /* ---- Additive<double>  (src/additive.h:11-71 + Minimizer note API,
- *      src/minimizer.h:111-187; physics() is out of scope) ------------------- */
+ *      src/minimizer.h:111-187; physics(): hz_add_physics_every below) -------- */
 typedef struct hz_add hz_add;
 /* Additive(Wave* = &cycle, voices, overtones, decay, harmonicity = 1, k = 0.1)  additive.h:24-36 */
 int hz_add_create(int voices, int overtones, double decay, double harmonicity, double k, int device,
@@ -308,6 +308,39 @@ int hz_add_set_stream(hz_add* h, void* hip_stream);
 int hz_add_set_target_groups(hz_add* h, int groups);
 int hz_add_profile(hz_add* h, int enable);
 int hz_add_profile_read(hz_add* h, double* ms, long* launches);
+
+/* Minimizer<T>::physics() (src/minimizer.h:61-108, src/particle.h) on the device: springs along each
+ * voice's overtone chain and gravity between partials of different active voices move the particle
+ * positions that Additive::tick() reads through freqmod(mtof(position)).
+ * The gravity law is a required argument, there is no default.  particle.h:119,121 call an
+ * unqualified abs on doubles:
+ *   HZ_GRAV_TRUNC  abs binds ::abs(int): cubed = |(int)(d d d)|, cutoff |(int)d| >= 0.5.  This is what
+ *                  the reference computes when built as oracle/Makefile builds it (g++, libstdc++).
+ *   HZ_GRAV_FABS   abs binds std::abs(double): the text as written (the author's platform, libc++).
+ * Positions follow the reference bit for bit under either law. */
+#define HZ_GRAV_TRUNC 1
+#define HZ_GRAV_FABS 2
+/* Block path.  period > 0: from now on hz_add_fill / hz_add_fill_device compute
+ *   n x { out[t] = operator()(); if (T >= period && T % period == 0) physics(); tick(); T++; }
+ * with T = samples since this call (period 2 is tests/additive.cpp's Metro<double>(24000)).
+ * period == 0: physics off; the static engine renders from the positions as moved.
+ * A bad law is HZ_E_INVALID; a sharded handle is HZ_E_UNSUPPORTED (physics needs every partial). */
+int hz_add_physics_every(hz_add* h, int period, int law);
+/* Per-sample path: one physics() step now; the next tick() reads the moved positions.  From here on
+ * fills of any length are served directly (no speculative block) until hz_add_physics_every(h, 0, law). */
+int hz_add_physics(hz_add* h, int law);
+/* operator()() without tick().  Like hz_add_physics it enters the per-sample path: the fills that
+ * follow are served directly until hz_add_physics_every(h, 0, law). */
+int hz_add_peek(hz_add* h, double* y);
+/* particles[v * overtones + j]() for every particle (voices x overtones doubles), synchronised */
+int hz_add_positions(hz_add* h, double* out);
+/* physics path split: banks of up to single_group_max particles (default 256, at most 1024) run all
+ * steps of a call in one workgroup; larger ones launch once per step with `tile` threads per
+ * workgroup (a multiple of 64 up to 1024, default 256).  0 = default. */
+int hz_add_tune_physics(hz_add* h, int single_group_max, int tile);
+/* with hz_add_profile on: milliseconds spent in the physics kernels and in the audio kernels of the
+ * physics path since hz_add_profile(h, 1) */
+int hz_add_physics_profile_read(hz_add* h, double* physics_ms, double* audio_ms);
 
 /* ---- Sinusoids<double>  (src/sinusoids.h:10-79), waveform cycle ------------ */
 typedef struct hz_sin hz_sin;

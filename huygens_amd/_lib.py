@@ -164,6 +164,23 @@ _SIGS = {
     "hz_add_positions": (I, [VP, PD]),
     "hz_add_tune_physics": (I, [VP, I, I]),
     "hz_add_physics_profile_read": (I, [VP, PD, PD]),
+    "hz_sub_create": (I, [I, I, I, D, D, D, D, I, C.POINTER(VP)]),
+    "hz_sub_destroy": (I, [VP]),
+    "hz_sub_request": (I, [VP, D, D, C.POINTER(I)]),
+    "hz_sub_release": (I, [VP, I]),
+    "hz_sub_makenote": (I, [VP, D, D, C.POINTER(I)]),
+    "hz_sub_endnote": (I, [VP, D]),
+    "hz_sub_physics_every": (I, [VP, I, I]),
+    "hz_sub_physics": (I, [VP, I]),
+    "hz_sub_process": (I, [VP, PD, PD, SZ]),
+    "hz_sub_process_device": (I, [VP, VP, VP, SZ]),
+    "hz_sub_peek": (I, [VP, PD, PD]),
+    "hz_sub_positions": (I, [VP, PD]),
+    "hz_sub_amplitudes": (I, [VP, PD]),
+    "hz_sub_set_stream": (I, [VP, VP]),
+    "hz_sub_tune_physics": (I, [VP, I, I]),
+    "hz_sub_profile": (I, [VP, I]),
+    "hz_sub_profile_read": (I, [VP, PD, PD, PD, PD]),
     "hz_sin_create": (I, [D, I, D, D, D, I, C.POINTER(VP)]),
     "hz_sin_destroy": (I, [VP]),
     "hz_sin_fundmod": (I, [VP, D]),

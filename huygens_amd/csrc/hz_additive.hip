@@ -584,16 +584,10 @@ struct PhaseBank {
 // ---------------------------------------------------------------------------
 // Additive<double>  (src/additive.h:11-71 + Minimizer note API, src/minimizer.h:111-181)
 // ---------------------------------------------------------------------------
-struct hz_add {
+struct hz_add : hz::MinNotes {   // the note layer: position covers all overtones; with physics on, the
+                                 // device copy (phys.d_x) is the one that moves
     PhaseBank bank;
-    int V = 0, O = 0;
-    double decay = 0, harmonicity = 1, norm = 1;
-    std::vector<double> active;     // Minimizer::active (amplitude targets)
-    std::vector<double> pitches;    // Minimizer::pitches
-    std::vector<double> guide;      // guides[v].position
-    std::vector<double> position;   // particles[v*O+j].position (all overtones); with physics on, the
-                                    // device copy (phys.d_x) is the one that moves
-    std::vector<double> equilibrium;   // springs[v*O+j].equilibrium
+    double decay = 0, norm = 1;
     // Minimizer::physics() (hz_minimizer.hip).  The device state exists from the first physics call
     // on; before it no particle has moved (velocity 0) and the host mirrors above are complete.
     struct Physics {
@@ -655,15 +649,7 @@ int phys_law_check(hz_add* h, int law) {
 }
 
 hz::MinParams phys_params(const hz_add* h) {
-    hz::MinParams p;
-    p.V = h->V;
-    p.O = h->O;
-    p.G = 1 * 50000;          // includes.h:34 FORCE; minimizer.h:56
-    p.eps = 0.0001;           // particle.h:108
-    p.k0 = 0.1 * 50000;       // minimizer.h:40
-    p.k1 = 1 * 50000;         // minimizer.h:45
-    p.drag = hz::relaxation(0.01);   // particle.h:23-27
-    return p;
+    return hz::min_params(h->V, h->O, 0.1 * 50000, 1 * 50000);   // minimizer.h:40, 45
 }
 
 // device rows of one voice after request(): position, equilibrium, velocity 0
@@ -825,10 +811,8 @@ int hz_add_create_shard(int voices, int overtones, int o_begin, int o_count, dou
     HZ_TRY(hz::select_device(device));
     hz_add* h = new (std::nothrow) hz_add();
     if (!h) return HZ_E_ALLOC;
-    h->V = voices;
-    h->O = overtones;
+    h->notes_init(voices, overtones, harmonicity);
     h->decay = decay;
-    h->harmonicity = harmonicity;
     // additive.h:27 normalization; oscillators are Oscillator(0, 0, 0.0001) (35)
     h->norm = decay != 1 ? (1 - std::pow(decay, overtones)) / (1 - decay) : overtones;
     int rc = h->bank.init(voices, overtones, o_begin, o_count, hz::relaxation(0.0001), hz::relaxation(k), device);
@@ -842,11 +826,6 @@ int hz_add_create_shard(int voices, int overtones, int o_begin, int o_count, dou
             h->bank.c[(size_t)v * o_count + jl] = std::pow(decay, o_begin + jl);
     h->bank.c_first = h->bank.c;
     h->bank.scale = 1.0 / (voices * h->norm);
-    h->active.assign(voices, 0.0);
-    h->pitches.assign(voices, 0.0);
-    h->guide.assign(voices, 0.0);
-    h->position.assign((size_t)voices * overtones, 0.0);
-    h->equilibrium.assign((size_t)voices * overtones, 0.0);
     *out = h;
     return HZ_OK;
 }
@@ -869,36 +848,7 @@ int hz_add_request(hz_add* h, double fundamental, double amplitude, int* voice_o
     if (!h) return HZ_E_INVALID;
     HZ_TRY(add_check(h));
     HZ_TRY(h->bank.settle());   // a speculative block rolls back to the consumed sample first
-    int voice = -1;
-    for (int i = 0; i < h->V; ++i)
-        if (!h->active[i]) {
-            voice = i;
-            break;
-        }
-    if (voice < 0) {  // steal the voice whose guide is nearest in pitch
-        const double pitch = 69 + std::log2(fundamental / 440.0) * 12;
-        double distance = 0;
-        int nearest = -1;
-        for (int i = 0; i < h->V; ++i) {
-            double offset = pitch - h->guide[i];
-            offset *= offset;
-            if (nearest < 0 || offset < distance) {
-                nearest = i;
-                distance = offset;
-            }
-        }
-        voice = nearest;
-    }
-    h->active[voice] = amplitude;
-    h->guide[voice] = 69 + std::log2(fundamental / 440.0) * 12;
-    double frequency = fundamental;
-    for (int j = 0; j < h->O; ++j) {
-        const double previous = frequency;
-        frequency = fundamental * (1 + std::pow((double)j / (h->O - 1), h->harmonicity) * (h->O - 1));
-        const double pitch = 69 + std::log2(frequency / 440.0) * 12;
-        h->position[(size_t)voice * h->O + j] = pitch;
-        h->equilibrium[(size_t)voice * h->O + j] = pitch - (69 + std::log2(previous / 440.0) * 12);
-    }
+    const int voice = h->request(fundamental, amplitude);
     h->bank.act[voice] = amplitude;
     add_retarget(h, voice);
     if (h->phys.ready) HZ_TRY(phys_upload_voice(h, voice));   // particles re-initialised: v = 0
@@ -911,18 +861,16 @@ int hz_add_release(hz_add* h, int voice) {
     if (!h) return HZ_E_INVALID;
     HZ_TRY(add_check(h));
     HZ_TRY(h->bank.settle());
+    h->release(voice);
     for (int i = 0; i < h->V; ++i)
-        if (voice < 0 || i == voice) {
-            h->active[i] = 0;
-            h->bank.act[i] = 0;
-        }
+        if (voice < 0 || i == voice) h->bank.act[i] = 0;
     return HZ_OK;
 }
 
 int hz_add_makenote(hz_add* h, double pitch, double amplitude, int* voice_out) {   // minimizer.h:174-179
     if (!h) return HZ_E_INVALID;
     int v = -1;
-    HZ_TRY(hz_add_request(h, 440.0 * std::pow(2, (pitch - 69) / 12), amplitude, &v));
+    HZ_TRY(hz_add_request(h, hz::MinNotes::mtof(pitch), amplitude, &v));
     if (v >= 0) h->pitches[v] = pitch;
     if (voice_out) *voice_out = v;
     return HZ_OK;

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "hz_fb_impl.h"
+#include "hz_resonant.h"
 #include "hz_rt.h"
 
 // per-band arithmetic in the restatement's order, without FMA contraction
@@ -71,54 +72,10 @@ __device__ __forceinline__ void cdiv(double a, double b, double c, double d, dou
     }
 }
 
-// x / SR correctly rounded without the IEEE divide sequence: q = x RN(1/SR), then one FMA
-// residual step (Markstein; x >= 0 normal here).  Equal to x / 48000.0 -- checked on the
-// host (tests/cpp/divcheck.c: random exponents, no mismatch).
-__device__ __forceinline__ double div_sr(double x) {
-    constexpr double inv = 1.0 / hz::kSR;
-    const double q = x * inv;
-    return __builtin_fma(__builtin_fma(-q, (double)hz::kSR, x), inv, q);
-}
-
-// cdiv(1, 0, c, d): both quotients share the denominator, so one IEEE reciprocal r = RN(1/den)
-// serves both: -1/den = -r exactly, and ratio/den is taken as RN(q0 + RN(ratio - den q0) r),
-// q0 = RN(ratio r) (one FMA residual step).  Markstein's exactness theorem needs q0 within 1 ulp,
-// which RN(ratio r) does not guarantee (up to ~1.5 ulp), so exactness is checked, not proven:
-// tests/cpp/divcheck.c compares it bit for bit with the Smith quotient on random resonant()
-// operands, generic operands and targeted hard cases (quotient mantissa near 2, reciprocal error
-// near 1/2 ulp) -- no mismatch in ~1e9 trials.  The sign of a zero may differ; nothing sees it.
-__device__ __forceinline__ void cdiv_one(double c, double d, double& x, double& y) {
-    const bool lt = fabs(c) < fabs(d);
-    const double ratio = lt ? c / d : d / c;
-    const double den = lt ? (c * ratio) + d : (d * ratio) + c;
-    const double r = 1.0 / den;
-    const double q0 = ratio * r;
-    const double q = __builtin_fma(__builtin_fma(-q0, den, ratio), r, q0);   // RN(ratio / den)
-    x = lt ? q : r;
-    y = lt ? -r : -q;
-}
-
-// subtractive.h:240-249
-// cos / sincos of an angle: the bounded-range kernels (< 1 ulp, hz_rt.h) for 0 <= x <= 2 PI -- every
-// audio frequency's 2 PI f / SR and 4 PI f / SR -- else libm
-__device__ __forceinline__ double tv_cos(double x) {
-    return (x >= 0.0 && x <= 6.2831853072) ? hz_rt::cos_0_2pi(x) : cos(x);
-}
-__device__ __forceinline__ void tv_sincos(double x, double* s, double* c) {
-    if (x >= 0.0 && x <= 6.2831853072) hz_rt::sincos_0_2pi(x, s, c);
-    else sincos(x, s, c);
-}
-
-__device__ __forceinline__ double resonant(double frequency, double Q) {
-    double s2, c2;
-    tv_sincos(div_sr(4 * hz::kPI * frequency), &s2, &c2);
-    const double ir = 0.0 * s2 - 1.0 * 0.0, ii = 0.0 * 0.0 + 1.0 * s2;   // 1.0i * sine2
-    const double dr = (Q - c2) - ir, di = -0.0 - ii;
-    double qr, qi;
-    cdiv_one(dr, di, qr, qi);
-    const double mr = 1.0 / (Q - 1) - qr, mi = 0.0 - qi;
-    return 1 / sqrt(hypot(mr, mi));
-}
+// resonant() and its helpers: hz_resonant.h (shared with hz_subtractive.hip)
+using hz_res::div_sr;
+using hz_res::resonant;
+using hz_res::tv_cos;
 
 template <int O, int KIND, int DIST>
 __global__ __launch_bounds__(kThreads) void fb_tv_kernel(TvArgs a) {

@@ -342,6 +342,46 @@ int hz_add_tune_physics(hz_add* h, int single_group_max, int tile);
  * physics path since hz_add_profile(h, 1) */
 int hz_add_physics_profile_read(hz_add* h, double* physics_ms, double* audio_ms);
 
+/* ---- Subtractive<double, N>  (src/subtractive.h:15-101, the MIMO variant; note API and physics()
+ *      from Minimizer, src/minimizer.h:61-187) ---------------------------------- */
+typedef struct hz_sub hz_sub;
+/* Subtractive(voices, overtones, decay, resonance = 0.99999, harmonicity = 1.0, k = 0.1) with
+ * `channels` = N: voices x overtones x channels Filter<T> resonators, retuned from the particle
+ * positions by every tick() of a voice whose amplitude is nonzero.  HZ_E_INVALID for voices < 1,
+ * overtones < 2 (request() divides by overtones - 1) or channels < 1; HZ_E_UNSUPPORTED for more
+ * than 8 channels. */
+int hz_sub_create(int voices, int overtones, int channels, double decay, double resonance, double harmonicity,
+                  double k, int device, hz_sub** out);
+int hz_sub_destroy(hz_sub* h);
+int hz_sub_request(hz_sub* h, double fundamental, double amplitude, int* voice);   /* minimizer.h:111-158 */
+int hz_sub_release(hz_sub* h, int voice);                                          /* 161-172, -1 = all */
+int hz_sub_makenote(hz_sub* h, double pitch, double amplitude, int* voice);        /* 174-179 */
+int hz_sub_endnote(hz_sub* h, double pitch);                                       /* 182-187 */
+/* period > 0: from now on hz_sub_process computes
+ *   n x { out[:, t] = operator()(in[:, t]); if (T >= period && T % period == 0) physics(); tick(); T++; }
+ * with T = samples since this call (period 32 is the reference programs' Metro<double>(SR / 32)).
+ * period == 0: no physics step inside a call.  law is HZ_GRAV_TRUNC or HZ_GRAV_FABS in either case,
+ * there is no default (HZ_E_INVALID otherwise). */
+int hz_sub_physics_every(hz_sub* h, int period, int law);
+/* one physics() step now; the next tick() reads the moved positions */
+int hz_sub_physics(hz_sub* h, int law);
+/* in and out are [channels][n], channel-major.  Filter state, envelopes and positions persist in
+ * the handle; n == 0 is a no-op. */
+int hz_sub_process(hz_sub* h, const double* in, double* out, size_t n);
+int hz_sub_process_device(hz_sub* h, const double* d_in, double* d_out, size_t n);
+/* operator()(in[channels]) without tick(): out[channels], nothing advances */
+int hz_sub_peek(hz_sub* h, const double* in, double* out);
+/* particles[v * overtones + j]() (voices x overtones doubles) and amplitudes[v] (voices doubles) */
+int hz_sub_positions(hz_sub* h, double* out);
+int hz_sub_amplitudes(hz_sub* h, double* out);
+int hz_sub_set_stream(hz_sub* h, void* hip_stream);
+/* as hz_add_tune_physics */
+int hz_sub_tune_physics(hz_sub* h, int single_group_max, int tile);
+/* with the profile on: milliseconds since hz_sub_profile(h, 1) in the physics kernels, the
+ * coefficient kernel, the resonator kernel and the reduce kernel */
+int hz_sub_profile(hz_sub* h, int enable);
+int hz_sub_profile_read(hz_sub* h, double* physics_ms, double* coef_ms, double* resonator_ms, double* reduce_ms);
+
 /* ---- Sinusoids<double>  (src/sinusoids.h:10-79), waveform cycle ------------ */
 typedef struct hz_sin hz_sin;
 /* Sinusoids(Wave*, fundamental, overtones, decay, harmonicity = 1, k = 2.0/SR) 16-31 */

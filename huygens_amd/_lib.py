@@ -209,6 +209,8 @@ _SIGS = {
     "hz_dly_modulate_back": (I, [VP, I, C.c_uint, C.c_uint, D]),
     "hz_dly_process": (I, [VP, VP, VP, SZ, I, I]),
     "hz_dly_process_device": (I, [VP, VP, VP, SZ, I, I]),
+    "hz_dly_process_tv": (I, [VP, VP, VP, SZ, I, I, VP, VP, VP, VP]),
+    "hz_dly_process_tv_device": (I, [VP, VP, VP, SZ, I, I, VP, VP, VP, VP]),
     "hz_dly_tick": (I, [VP, C.c_ulong]),
     "hz_dly_origin": (I, [VP, C.POINTER(C.c_uint)]),
     "hz_dly_info": (I, [VP, C.POINTER(L), C.POINTER(C.c_uint)]),

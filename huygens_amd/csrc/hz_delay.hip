@@ -166,6 +166,178 @@ __global__ __launch_bounds__(256) void dly_mix_kernel(const T* __restrict__ y, l
     out[j] = s / (T)N;
 }
 
+// ---- per-sample tap streams (hz_dly_process_tv) -------------------------------------------
+// Every tap has a {time, gain} per sample, so the host cannot resolve {thr, ages} in advance:
+// the kernels evaluate buffer.h:42-46 themselves, idx = (uint32)(o - c + size) % size with
+// c = (int)(T)time and o the sample's own origin, one 32-bit remainder per read (tv_rem).  The
+// slot's age (o - idx mod size) picks the source exactly as above: the call's arrays when
+// age <= j, else the rings (written only at the end of the call).  DESIGN.md 4.9.
+struct DlyTvArgs {
+    const void* in;       // mono [n] or line-major [N][n]
+    void* y;              // line outputs [N][n]
+    const unsigned* ft;   // [N][S][n]
+    const void* fg;       // [N][S][n] T
+    const unsigned* bt;   // [N][S][n], or the staged feedback taps [N][S] (bstride 1, bstep 0)
+    const void* bg;
+    void* ring_x;
+    void* ring_y;
+    long n, Lc;
+    long k0, k1;          // sub-block range of this launch
+    long bstride;         // elements between two taps' back streams
+    unsigned bstep;       // elements between two samples of one (1, or 0: static)
+    int S, in_per_line, commit;
+    unsigned size, rcp, o0;   // rcp: tv_rem's reciprocal of size
+};
+
+// w % size without the divide: with rcp = min(floor(2^32 / size), 2^32 - 1) the quotient estimate
+// umulhi(w, rcp) is the true one or one less (w * (2^32 / size - rcp) < 2^32), so one conditional
+// subtraction makes the remainder exact for every 32-bit w
+__device__ __forceinline__ unsigned tv_rem(unsigned w, unsigned size, unsigned rcp) {
+    const unsigned r = w - __umulhi(w, rcp) * size;
+    return r >= size ? r - size : r;
+}
+
+template <typename T>
+__device__ __forceinline__ unsigned tv_slot(unsigned time, unsigned o, unsigned size, unsigned rcp) {
+    const int c = (int)(T)time;
+    return tv_rem(o - (unsigned)c + size, size, rcp);
+}
+
+__device__ __forceinline__ unsigned tv_age(unsigned o, unsigned idx, unsigned size) {
+    return o >= idx ? o - idx : o + size - idx;
+}
+
+template <typename T>
+__device__ __forceinline__ bool tv_time_ok(unsigned t) {   // (int)(T)t defined, as set_tap
+    return t <= (sizeof(T) == 4 ? 2147483520u : 2147483647u);
+}
+
+// One pass over the streams: rec[0] stays all ones unless a time is out of (int)(T)t's range,
+// rec[1] = the smallest age >= 1 of a live feedback read (gain != 0, time != 0), each sample at
+// its own origin; last_t/last_g [2][NS] = the streams' last row (forward, then back when given).
+// blockIdx.y strides the taps, blockIdx.x the samples.
+template <typename T>
+__global__ __launch_bounds__(256) void dly_tv_scan_kernel(DlyTvArgs a, int NS, int has_back, unsigned* __restrict__ rec,
+                                                          unsigned* __restrict__ last_t, T* __restrict__ last_g) {
+    unsigned mn = 0xffffffffu;
+    bool bad = false;
+    for (int tap = blockIdx.y; tap < NS; tap += gridDim.y) {
+        const unsigned* __restrict__ ftp = a.ft + (long)tap * a.n;
+        const unsigned* __restrict__ btp = a.bt + (long)tap * a.bstride;
+        const T* __restrict__ bgp = (const T*)a.bg + (long)tap * a.bstride;
+        for (long j = (long)blockIdx.x * blockDim.x + threadIdx.x; j < a.n; j += (long)gridDim.x * blockDim.x) {
+            const unsigned tf = ftp[j], tb = btp[j * a.bstep];
+            const T g = bgp[j * a.bstep];
+            bad = bad || !tv_time_ok<T>(tf) || !tv_time_ok<T>(tb);
+            if (tb != 0u && g != (T)0) {
+                const unsigned o = tv_rem(a.o0 + (unsigned)j, a.size, a.rcp);
+                const unsigned age = tv_age(o, tv_slot<T>(tb, o, a.size, a.rcp), a.size);
+                if (age != 0u) mn = min(mn, age);
+            }
+            if (j == a.n - 1) {
+                last_t[tap] = tf;
+                last_g[tap] = ((const T*)a.fg)[(long)tap * a.n + j];
+                if (has_back) {
+                    last_t[NS + tap] = tb;
+                    last_g[NS + tap] = g;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) mn = min(mn, (unsigned)__shfl_xor((int)mn, d));
+    const bool any_bad = __any(bad) != 0;
+    // one atomic per workgroup at most: every wave of a long call hitting the one word serialises
+    __shared__ unsigned s_mn[4];
+    __shared__ int s_bad[4];
+    if ((threadIdx.x & 63) == 0) s_mn[threadIdx.x >> 6] = mn, s_bad[threadIdx.x >> 6] = any_bad;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        mn = min(min(s_mn[0], s_mn[1]), min(s_mn[2], s_mn[3]));
+        if (mn != 0xffffffffu) atomicMin(&rec[1], mn);
+        if (s_bad[0] | s_bad[1] | s_bad[2] | s_bad[3]) atomicAnd(&rec[0], 0u);
+    }
+}
+
+template <typename T, int kBatch>
+__global__ __launch_bounds__(kThreads) void dly_tv_line_kernel(DlyTvArgs a) {
+#pragma clang fp contract(off)
+    const int line = blockIdx.y;
+    const int Gt = gridDim.x, g = blockIdx.x;
+    const int S = a.S;
+    const unsigned size = a.size;
+    const T* __restrict__ xin = (const T*)a.in + (a.in_per_line ? (long)line * a.n : 0);
+    T* yout = (T*)a.y + (long)line * a.n;
+    T* rx = (T*)a.ring_x + (long)line * size;
+    T* ry = (T*)a.ring_y + (long)line * size;
+
+    for (long k = a.k0; k < a.k1; ++k) {
+        const long s0 = k * a.Lc, s1 = min(a.n, s0 + a.Lc);
+        const long per = (s1 - s0 + Gt - 1) / Gt;
+        const long b0 = s0 + g * per, b1 = min(s1, b0 + per);
+        // kBatch samples per thread, every gather of a tap issued before any store (the stores of
+        // this sub-block are never read in it: a live feedback age is 0 or >= Lc)
+        for (long base = b0; base < b1; base += (long)blockDim.x * kBatch) {
+            unsigned jj[kBatch];   // n < 2^31: 32-bit offsets from the taps' uniform stream bases
+            unsigned oo[kBatch];
+            T acc[kBatch];
+#pragma unroll
+            for (int m = 0; m < kBatch; ++m) {
+                jj[m] = (unsigned)min(base + threadIdx.x + (long)m * blockDim.x, b1 - 1);
+                oo[m] = tv_rem(a.o0 + (unsigned)jj[m], size, a.rcp);
+                acc[m] = (T)0;
+            }
+            for (int i = 0; i < S; ++i) {
+                const long tap = (long)line * S + i;
+                const unsigned* __restrict__ ftp = a.ft + tap * a.n;
+                const T* __restrict__ fgp = (const T*)a.fg + tap * a.n;
+                const unsigned* __restrict__ btp = a.bt + tap * a.bstride;
+                const T* __restrict__ bgp = (const T*)a.bg + tap * a.bstride;
+                T fx[kBatch], b[kBatch], yv[kBatch];
+#pragma unroll
+                for (int m = 0; m < kBatch; ++m) {
+                    const unsigned o = oo[m];
+                    const unsigned xi = tv_slot<T>(ftp[jj[m]], o, size, a.rcp), af = tv_age(o, xi, size);
+                    const T* src = (af <= jj[m]) ? xin + (jj[m] - af) : rx + xi;
+                    fx[m] = *src;   // one branch-free gather: the pointer is selected, not the load
+                }
+#pragma unroll
+                for (int m = 0; m < kBatch; ++m) fx[m] = fgp[jj[m]] * fx[m];
+#pragma unroll
+                for (int m = 0; m < kBatch; ++m) {
+                    const unsigned o = oo[m], tb = btp[jj[m] * a.bstep];
+                    b[m] = (tb == 0u) ? (T)0 : bgp[jj[m] * a.bstep];   // zero-time feedback -> {0, 0}
+                    const bool live = b[m] != (T)0;
+                    const unsigned yi = tv_slot<T>(tb, o, size, a.rcp), ab = tv_age(o, yi, size);
+                    // a dead tap reads its own (valid) ring slot and drops the value; age 0 reads
+                    // yout[j] (stale) and takes the partial sum instead
+                    const T* src = !live ? ry + o : (ab <= jj[m]) ? yout + (jj[m] - ab) : ry + yi;
+                    const T v = *src;
+                    yv[m] = !live ? (T)0 : (ab == 0u) ? acc[m] : v;
+                }
+#pragma unroll
+                for (int m = 0; m < kBatch; ++m) {
+                    const T by = b[m] * yv[m];
+                    acc[m] = acc[m] + (fx[m] - by);
+                }
+            }
+#pragma unroll
+            for (int m = 0; m < kBatch; ++m)
+                if (base + threadIdx.x + (long)m * blockDim.x < b1) yout[jj[m]] = acc[m];
+        }
+        if (k + 1 < a.k1) __syncthreads();   // sub-block k visible to k+1 (same CU, same L1)
+    }
+    if (a.commit) {   // single-launch mode: one workgroup per line, all reads of the call done
+        __syncthreads();
+        const long j0 = a.n > (long)size ? a.n - (long)size : 0;
+        for (long j = j0 + threadIdx.x; j < a.n; j += blockDim.x) {
+            const unsigned slot = (unsigned)((a.o0 + (unsigned long)j) % size);
+            rx[slot] = xin[j];
+            ry[slot] = yout[j];
+        }
+    }
+}
+
 }  // namespace
 
 struct hz_dly {
@@ -180,6 +352,12 @@ struct hz_dly {
     hz::DevBuf<int4> d_taps;
     hz::DevBuf<char> d_gains, d_rx, d_ry;   // doubles or floats (elem() bytes each)
     hz::DevBuf<char> d_y, d_in, d_out;
+    // hz_dly_process_tv: the scan's record {valid, min age, last row} on the device and pinned, the
+    // staged feedback taps as the kernels read them (null back streams), the host entry's streams
+    hz::DevBuf<char> d_tvrec, d_tvback, d_sfg, d_sbg;
+    hz::DevBuf<unsigned> d_sft, d_sbt;
+    hz::PinBuf<char> p_tvrec;
+    std::vector<char> tv_back;
     hipStream_t stream = nullptr;
     bool own_stream = false;
     bool prof = false;
@@ -254,6 +432,22 @@ int dly_upload(hz_dly* h) {
     return HZ_OK;
 }
 
+// with profiling on: the next pair of timing events, the first one recorded (else *e stays null)
+int dly_prof_begin(hz_dly* h, hipEvent_t** e) {
+    *e = nullptr;
+    if (!h->prof) return HZ_OK;
+    if (h->ev_used + 2 > h->ev.size())
+        for (int q = 0; q < 128; ++q) {
+            hipEvent_t ne;
+            HZ_TRY_HIP(hz::prof_event_create(&ne));
+            h->ev.push_back(ne);
+        }
+    *e = &h->ev[h->ev_used];
+    h->ev_used += 2;
+    HZ_TRY_HIP(hipEventRecord((*e)[0], h->stream));
+    return HZ_OK;
+}
+
 template <typename T>
 int dly_launch_t(hz_dly* h, const void* d_in, void* d_out, long n, int in_per_line, int mix) {
     const int N = h->N;
@@ -274,17 +468,7 @@ int dly_launch_t(hz_dly* h, const void* d_in, void* d_out, long n, int in_per_li
     if (mode == 2 && gt_max == 1) mode = 1;
 
     hipEvent_t* e = nullptr;
-    if (h->prof) {
-        if (h->ev_used + 2 > h->ev.size())
-            for (int q = 0; q < 128; ++q) {
-                hipEvent_t ne;
-                HZ_TRY_HIP(hz::prof_event_create(&ne));
-                h->ev.push_back(ne);
-            }
-        e = &h->ev[h->ev_used];
-        h->ev_used += 2;
-        HZ_TRY_HIP(hipEventRecord(e[0], h->stream));
-    }
+    HZ_TRY(dly_prof_begin(h, &e));
     DlyArgs a;
     a.in = d_in;
     a.y = y;
@@ -341,6 +525,153 @@ int dly_launch(hz_dly* h, const void* d_in, void* d_out, long n, int in_per_line
     HZ_TRY(dly_upload(h));
     return h->is_float ? dly_launch_t<float>(h, d_in, d_out, n, in_per_line, mix)
                        : dly_launch_t<double>(h, d_in, d_out, n, in_per_line, mix);
+}
+
+// hz_dly_process_tv on device pointers: scan, one read-back of its record, then the sub-blocks.
+// Nothing of the handle changes before the record is known to be valid.
+template <typename T>
+int dly_tv_launch_t(hz_dly* h, const void* d_in, void* d_out, long n, int in_per_line, int mix, const unsigned* ft,
+                    const void* fg, const unsigned* bt, const void* bg) {
+    const int N = h->N, S = h->S;
+    const size_t NS = (size_t)N * S;
+    // record: {valid, min age} | last times [2][NS] | last gains [2][NS] (8-byte aligned)
+    const size_t off_t = 2 * sizeof(unsigned);
+    const size_t off_g = (off_t + 2 * NS * sizeof(unsigned) + 7) / 8 * 8;
+    const size_t rec_bytes = off_g + 2 * NS * sizeof(T);
+    HZ_TRY(h->d_tvrec.reserve(rec_bytes));
+    HZ_TRY(h->p_tvrec.reserve(rec_bytes));
+
+    DlyTvArgs a;
+    a.in = d_in;
+    a.ft = ft;
+    a.fg = fg;
+    a.bt = bt;
+    a.bg = bg;
+    a.bstride = n;
+    a.bstep = 1;
+    if (!bt) {   // the staged feedback taps, as given ([NS] gains, then [NS] times), read by every sample
+        h->tv_back.resize(NS * (sizeof(T) + sizeof(unsigned)));
+        T* sg = (T*)h->tv_back.data();
+        unsigned* st = (unsigned*)(h->tv_back.data() + NS * sizeof(T));
+        for (size_t q = 0; q < NS; ++q) sg[q] = (T)h->bg[q], st[q] = h->bt[q];
+        HZ_TRY(h->d_tvback.reserve(h->tv_back.size()));
+        HZ_TRY_HIP(hipMemcpyAsync(h->d_tvback, h->tv_back.data(), h->tv_back.size(), hipMemcpyHostToDevice, h->stream));
+        a.bg = h->d_tvback.get();
+        a.bt = (const unsigned*)(h->d_tvback.get() + NS * sizeof(T));
+        a.bstride = 1;
+        a.bstep = 0;
+    }
+    a.ring_x = h->d_rx;
+    a.ring_y = h->d_ry;
+    a.n = n;
+    a.Lc = n;
+    a.k0 = a.k1 = 0;
+    a.S = S;
+    a.in_per_line = in_per_line;
+    a.commit = 0;
+    a.size = h->size;
+    a.rcp = (unsigned)std::min<unsigned long>((1ul << 32) / h->size, 0xfffffffful);
+    a.o0 = h->origin;
+    a.y = nullptr;
+
+    char* rec = h->d_tvrec;
+    hipEvent_t* e = nullptr;
+    HZ_TRY_HIP(hipMemsetAsync(rec, 0xff, off_t, h->stream));
+    HZ_TRY(dly_prof_begin(h, &e));
+    const unsigned sgx = (unsigned)std::min<long>((n + 255) / 256, 64);   // about 1024 workgroups at most
+    const dim3 sgrid(sgx, (unsigned)std::min<size_t>(NS, std::max(1u, 1024u / sgx)));
+    hipLaunchKernelGGL(dly_tv_scan_kernel<T>, sgrid, dim3(256), 0, h->stream, a, (int)NS, bt ? 1 : 0, (unsigned*)rec,
+                       (unsigned*)(rec + off_t), (T*)(rec + off_g));
+    HZ_TRY_HIP(hipGetLastError());
+    if (e) HZ_TRY_HIP(hipEventRecord(e[1], h->stream));
+    HZ_TRY_HIP(hipMemcpyAsync(h->p_tvrec, rec, rec_bytes, hipMemcpyDeviceToHost, h->stream));
+    HZ_TRY_HIP(hipStreamSynchronize(h->stream));
+    const unsigned* hrec = (const unsigned*)h->p_tvrec.get();
+    if (hrec[0] != 0xffffffffu) {
+        hz::set_error("hz_dly_process_tv: a delay time in the stream exceeds the int range of Buffer::operator() (buffer.h:42)");
+        return HZ_E_INVALID;
+    }
+
+    void* y = d_out;
+    if (mix) {
+        HZ_TRY(h->d_y.reserve(sizeof(T) * (size_t)N * n));
+        y = h->d_y;
+    }
+    a.y = y;
+    const long Lc = (hrec[1] != 0xffffffffu) ? std::min<long>((long)hrec[1], n) : n;
+    const long nsub = (n + Lc - 1) / Lc;
+    const long gt_max = std::max<long>(1, std::min<long>((Lc + kThreads - 1) / kThreads,
+                                                         (2L * h->target_groups + N - 1) / N));
+    int mode = h->split;   // the rule of dly_launch_t
+    if (mode == 0) mode = (gt_max > 1 && (nsub <= 8 || N < h->target_groups)) ? 2 : 1;
+    if (mode == 2 && gt_max == 1) mode = 1;
+    a.Lc = Lc;
+    HZ_TRY(dly_prof_begin(h, &e));
+    const long slice = (mode == 1) ? Lc : (Lc + gt_max - 1) / gt_max;
+    // samples per thread per pass: 4 at most -- a sample holds six loads per tap here (two times, two
+    // gains, two gathers) against dly_line_kernel's two, and 8 samples spill the 128 registers that
+    // 1024 threads leave (472 bytes of scratch per lane in double)
+    auto kern = slice >= 4L * kThreads ? dly_tv_line_kernel<T, 4>
+                                       : (slice > kThreads ? dly_tv_line_kernel<T, 2> : dly_tv_line_kernel<T, 1>);
+    if (mode == 1) {
+        a.k0 = 0;
+        a.k1 = nsub;
+        a.commit = 1;
+        hipLaunchKernelGGL(kern, dim3(1, N), dim3(kThreads), 0, h->stream, a);
+        HZ_TRY_HIP(hipGetLastError());
+    } else {
+        for (long k = 0; k < nsub; ++k) {
+            a.k0 = k;
+            a.k1 = k + 1;
+            hipLaunchKernelGGL(kern, dim3((unsigned)gt_max, N), dim3(kThreads), 0, h->stream, a);
+            HZ_TRY_HIP(hipGetLastError());
+        }
+        DlyArgs c{};
+        c.in = d_in;
+        c.y = y;
+        c.ring_x = h->d_rx;
+        c.ring_y = h->d_ry;
+        c.n = n;
+        c.in_per_line = in_per_line;
+        c.size = h->size;
+        c.o0 = h->origin;
+        const long span = std::min<long>(n, (long)h->size);
+        const unsigned gx = (unsigned)std::max<long>(1, std::min<long>((span + 255) / 256, 64));
+        hipLaunchKernelGGL(dly_commit_kernel<T>, dim3(gx, N), dim3(256), 0, h->stream, c);
+        HZ_TRY_HIP(hipGetLastError());
+    }
+    if (e) HZ_TRY_HIP(hipEventRecord(e[1], h->stream));
+    if (mix) {
+        hipLaunchKernelGGL(dly_mix_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
+                           (const T*)y, n, N, (T*)d_out);
+        HZ_TRY_HIP(hipGetLastError());
+    }
+    // the staged taps are now the streams' last row, as after the loop's last modulate_*
+    const unsigned* lt = (const unsigned*)(h->p_tvrec.get() + off_t);
+    const T* lg = (const T*)(h->p_tvrec.get() + off_g);
+    for (size_t q = 0; q < NS; ++q) {
+        h->ft[q] = lt[q];
+        h->fg[q] = (double)lg[q];
+        if (bt) {
+            h->bt[q] = lt[NS + q];
+            h->bg[q] = lt[NS + q] ? (double)lg[NS + q] : 0.0;   // zero-time feedback -> {0, 0}
+        }
+    }
+    h->dirty = true;
+    h->origin = (unsigned)(((unsigned long)h->origin + (unsigned long)n) % h->size);
+    h->launches += h->prof ? 1 : 0;
+    h->pending = true;
+    return HZ_OK;
+}
+
+int dly_tv_launch(hz_dly* h, const void* d_in, void* d_out, long n, int in_per_line, int mix, const unsigned* ft,
+                  const void* fg, const unsigned* bt, const void* bg) {
+    if (n >= (1L << 31)) {
+        hz::set_error("hz_dly_process_tv: n must be < 2^31 per call");
+        return HZ_E_INVALID;
+    }
+    return h->is_float ? dly_tv_launch_t<float>(h, d_in, d_out, n, in_per_line, mix, ft, fg, bt, bg)
+                       : dly_tv_launch_t<double>(h, d_in, d_out, n, in_per_line, mix, ft, fg, bt, bg);
 }
 
 int set_tap(hz_dly* h, int line, int back, unsigned i, unsigned t, double g) {
@@ -495,6 +826,48 @@ int hz_dly_process(hz_dly* h, const void* in, void* out, size_t n, int in_per_li
     HZ_TRY(h->d_out.reserve(out_bytes));
     HZ_TRY_HIP(hipMemcpyAsync(h->d_in, in, in_bytes, hipMemcpyHostToDevice, h->stream));
     HZ_TRY(dly_launch(h, h->d_in, h->d_out, (long)n, in_per_line, mix));
+    HZ_TRY_HIP(hipMemcpyAsync(out, h->d_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    HZ_TRY_HIP(hipStreamSynchronize(h->stream));
+    return HZ_OK;
+}
+
+int hz_dly_process_tv_device(hz_dly* h, const void* d_in, void* d_out, size_t n, int in_per_line, int mix,
+                             const unsigned* d_ft, const void* d_fg, const unsigned* d_bt, const void* d_bg) {
+    HZ_TRY(dly_check(h));
+    if (n == 0) return HZ_OK;
+    if (!d_in || !d_out || !d_ft || !d_fg || (d_bt == nullptr) != (d_bg == nullptr)) {
+        hz::set_error("hz_dly_process_tv: null pointer, or one of the back streams without the other");
+        return HZ_E_INVALID;
+    }
+    return dly_tv_launch(h, d_in, d_out, (long)n, in_per_line, mix, d_ft, d_fg, d_bt, d_bg);
+}
+
+int hz_dly_process_tv(hz_dly* h, const void* in, void* out, size_t n, int in_per_line, int mix, const unsigned* ft,
+                      const void* fg, const unsigned* bt, const void* bg) {
+    HZ_TRY(dly_check(h));
+    if (n == 0) return HZ_OK;
+    if (!in || !out || !ft || !fg || (bt == nullptr) != (bg == nullptr)) {
+        hz::set_error("hz_dly_process_tv: null pointer, or one of the back streams without the other");
+        return HZ_E_INVALID;
+    }
+    const size_t in_bytes = h->elem() * n * (in_per_line ? h->N : 1);
+    const size_t out_bytes = h->elem() * n * (mix ? 1 : h->N);
+    const size_t taps = (size_t)h->N * h->S * n;
+    HZ_TRY(h->d_in.reserve(in_bytes));
+    HZ_TRY(h->d_out.reserve(out_bytes));
+    HZ_TRY(h->d_sft.reserve(taps));
+    HZ_TRY(h->d_sfg.reserve(h->elem() * taps));
+    HZ_TRY_HIP(hipMemcpyAsync(h->d_in, in, in_bytes, hipMemcpyHostToDevice, h->stream));
+    HZ_TRY_HIP(hipMemcpyAsync(h->d_sft, ft, sizeof(unsigned) * taps, hipMemcpyHostToDevice, h->stream));
+    HZ_TRY_HIP(hipMemcpyAsync(h->d_sfg, fg, h->elem() * taps, hipMemcpyHostToDevice, h->stream));
+    if (bt) {
+        HZ_TRY(h->d_sbt.reserve(taps));
+        HZ_TRY(h->d_sbg.reserve(h->elem() * taps));
+        HZ_TRY_HIP(hipMemcpyAsync(h->d_sbt, bt, sizeof(unsigned) * taps, hipMemcpyHostToDevice, h->stream));
+        HZ_TRY_HIP(hipMemcpyAsync(h->d_sbg, bg, h->elem() * taps, hipMemcpyHostToDevice, h->stream));
+    }
+    HZ_TRY(dly_tv_launch(h, h->d_in, h->d_out, (long)n, in_per_line, mix, h->d_sft, h->d_sfg,
+                         bt ? h->d_sbt.get() : nullptr, bt ? (const void*)h->d_sbg.get() : nullptr));
     HZ_TRY_HIP(hipMemcpyAsync(out, h->d_out, out_bytes, hipMemcpyDeviceToHost, h->stream));
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     return HZ_OK;

@@ -2,7 +2,8 @@
 
 Delay<T> (src/delay.h:10-108, rings of src/buffer.h:9-86): Delay(sparsity, time),
 coefficients(forward, back) with (uint time, T gain) pairs, modulate_forward/back,
-operator()(x)/tick() -- here process(x) over a block.  Delaybank is N independent lines
+operator()(x)/tick() -- here process(x) over a block, and process_tv(x, streams) for taps that
+change every sample inside the block.  Delaybank is N independent lines
 (the reference's src/delaybank.h is a stub; SURVEY.md a21 gives the definition).
 """
 from __future__ import annotations
@@ -26,7 +27,7 @@ class Delaybank:
         h = C.c_void_p()
         self.dtype = np.dtype(dtype)
         check(lib.hz_dly_create(lines, sparsity, time, 1 if self.dtype == np.float32 else 0, device, C.byref(h)))
-        self._h, self._lib, self.lines = h, lib, lines
+        self._h, self._lib, self.lines, self.sparsity = h, lib, lines, sparsity
 
     def close(self):
         if getattr(self, "_h", None):
@@ -80,6 +81,42 @@ class Delaybank:
     def process_device(self, in_ptr: int, out_ptr: int, n: int, per_line: bool = False, mix: bool = False):
         check(self._lib.hz_dly_process_device(self._h, C.c_void_p(in_ptr), C.c_void_p(out_ptr), n,
                                               1 if per_line else 0, 1 if mix else 0))
+
+    def _stream(self, a, n, dtype, name):
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if a.shape != (self.lines, self.sparsity, n):
+            raise ValueError(f"{name}: shape {a.shape}, expected [lines, sparsity, n] = "
+                             f"{(self.lines, self.sparsity, n)}")
+        return a
+
+    def process_tv(self, x, ft, fg, bt=None, bg=None, mix: bool = False) -> np.ndarray:
+        """process() with a tap stream: before sample t every tap (l, i) becomes
+        {ft[l, i, t], fg[l, i, t]} (modulate_forward) and, with bt/bg, {bt[l, i, t], bg[l, i, t]}
+        (modulate_back; a back time of 0 is the tap {0, 0}).  Streams are [lines, sparsity, n],
+        times uint32 and gains the bank's dtype; without bt/bg the staged feedback taps stay.
+        Afterwards the staged taps are the streams' last row (hz_dly_process_tv)."""
+        x = np.ascontiguousarray(x, dtype=self.dtype)
+        per_line = x.ndim == 2
+        if per_line and x.shape[0] != self.lines:
+            raise ValueError("per-line input must have one row per line")
+        n = x.shape[-1]
+        ft = self._stream(ft, n, np.uint32, "ft")
+        fg = self._stream(fg, n, self.dtype, "fg")
+        bt = None if bt is None else self._stream(bt, n, np.uint32, "bt")
+        bg = None if bg is None else self._stream(bg, n, self.dtype, "bg")
+        out = np.zeros(n if mix else (self.lines, n), dtype=self.dtype)
+        if n:
+            p = [C.c_void_p(a.ctypes.data) if a is not None else None for a in (ft, fg, bt, bg)]
+            check(self._lib.hz_dly_process_tv(self._h, C.c_void_p(x.ctypes.data), C.c_void_p(out.ctypes.data), n,
+                                              1 if per_line else 0, 1 if mix else 0, *p))
+        return out
+
+    def process_tv_device(self, in_ptr: int, out_ptr: int, n: int, ft_ptr: int, fg_ptr: int, bt_ptr: int | None = None,
+                          bg_ptr: int | None = None, per_line: bool = False, mix: bool = False):
+        """process_tv on device pointers (streams [lines, sparsity, n], time fastest)."""
+        check(self._lib.hz_dly_process_tv_device(self._h, C.c_void_p(in_ptr), C.c_void_p(out_ptr), n,
+                                                 1 if per_line else 0, 1 if mix else 0, C.c_void_p(ft_ptr),
+                                                 C.c_void_p(fg_ptr), C.c_void_p(bt_ptr or 0), C.c_void_p(bg_ptr or 0)))
 
     def tick(self, count: int = 1):
         """tick() without operator() (delay.h:92-97), count times: both rings' origins move and
@@ -138,6 +175,11 @@ class Delay(Delaybank):
 
     def process(self, x) -> np.ndarray:  # noqa: D102
         return super().process(np.asarray(x).reshape(-1))[0]
+
+    def process_tv(self, x, ft, fg, bt=None, bg=None) -> np.ndarray:
+        """One line: streams [sparsity, n] (or [1, sparsity, n])."""
+        one = [None if a is None else np.asarray(a)[None] if np.ndim(a) == 2 else a for a in (ft, fg, bt, bg)]
+        return super().process_tv(np.asarray(x).reshape(-1), *one)[0]
 
     def __call__(self, x) -> float:
         """`y = delay(x); delay.tick();` (tests/delay.cpp:22-27) through the per-sample server"""

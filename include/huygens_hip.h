@@ -437,6 +437,19 @@ int hz_dly_modulate_back(hz_dly* h, int line, unsigned n, unsigned time, double 
  * the mixdown sum_k y_k / N, summed in line order in T (mix 1). */
 int hz_dly_process(hz_dly* h, const void* in, void* out, size_t n, int in_per_line, int mix);
 int hz_dly_process_device(hz_dly* h, const void* d_in, void* d_out, size_t n, int in_per_line, int mix);
+/* the same n samples with a {time, gain} for every tap at every sample: bit for bit
+ *     for t < n: { modulate_forward(l, i, {ft[l][i][t], fg[l][i][t]}) and, with a back stream,
+ *                  modulate_back(l, i, {bt[l][i][t], bg[l][i][t]}) for every line l, tap i;
+ *                  y[:, t] = line(x[t]); tick(); }
+ * (delay.h:57-97; a back time of 0 makes the tap {0,0} whatever its gain).  Each stream is
+ * [N][S][n], time fastest; times unsigned, gains T.  bt and bg come together or are both null:
+ * then the staged feedback taps apply through the call and stay.  Afterwards the staged taps are
+ * the streams' last row.  A time (int)(T)t cannot hold returns HZ_E_INVALID and changes nothing.
+ * One small device-to-host copy and one stream synchronisation per call (also in the _device form). */
+int hz_dly_process_tv(hz_dly* h, const void* in, void* out, size_t n, int in_per_line, int mix,
+                      const unsigned* ft, const void* fg, const unsigned* bt, const void* bg);
+int hz_dly_process_tv_device(hz_dly* h, const void* d_in, void* d_out, size_t n, int in_per_line, int mix,
+                             const unsigned* d_ft, const void* d_fg, const unsigned* d_bt, const void* d_bg);
 /* one sample of every line, `y_k = line_k(x); tick();` (delay.h:71-97), through the device's
  * per-sample server (a resident kernel shared by every handle of the process; no launch per
  * sample): in = one T (in_per_line 0) or N T, out = N T.  Bit-identical to hz_dly_process(n = 1). */

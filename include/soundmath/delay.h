@@ -65,6 +65,15 @@ public:
     void process(const T* in, T* out, std::size_t n, bool mix, bool per_line_input = false) {
         detail::check(hz_dly_process(h_.get(), in, out, n, per_line_input ? 1 : 0, mix ? 1 : 0), "Delaybank::process");
     }
+    // process() with taps that change every sample: before sample t every tap (l, i) is set as by
+    // modulate_forward(l, i, {ft[(l S + i) n + t], fg[...]}) and, with back streams, modulate_back
+    // (src/delay.h:57-68); the streams are [N][S][n], time fastest.  Without bt/bg the feedback
+    // taps stay as they are.  Afterwards the taps are the streams' last row.
+    void process_stream(const T* in, T* out, std::size_t n, bool mix, bool per_line_input, const unsigned* ft,
+                        const T* fg, const unsigned* bt = nullptr, const T* bg = nullptr) {
+        detail::check(hz_dly_process_tv(h_.get(), in, out, n, per_line_input ? 1 : 0, mix ? 1 : 0, ft, fg, bt, bg),
+                      "Delaybank::process_stream");
+    }
     hz_dly* native() const { return h_.get(); }
 
 private:
@@ -85,6 +94,11 @@ public:
     T operator()(T sample) { return bank_(&sample)(0); }
     void tick() { bank_.tick(); }
     void process(const T* in, T* out, std::size_t n) { bank_.process(in, out, n, false); }
+    // streams [S][n]: see Delaybank::process_stream
+    void process_stream(const T* in, T* out, std::size_t n, const unsigned* ft, const T* fg,
+                        const unsigned* bt = nullptr, const T* bg = nullptr) {
+        bank_.process_stream(in, out, n, false, false, ft, fg, bt, bg);
+    }
 
 private:
     Delaybank<T, 1> bank_;

@@ -221,6 +221,7 @@ _SIGS = {
     "hz_dly_profile": (I, [VP, I]),
     "hz_dly_profile_read": (I, [VP, PD, C.POINTER(L)]),
     "hz_stft_create": (I, [I, I, I, I, D, D, I, C.POINTER(VP)]),
+    "hz_stft_create_long": (I, [I, I, I, I, D, D, I, C.POINTER(VP)]),
     "hz_stft_destroy": (I, [VP]),
     "hz_stft_set_processor": (I, [VP, VP]),
     "hz_stft_process_block": (I, [VP, PD, PD, PD, PD, SZ]),

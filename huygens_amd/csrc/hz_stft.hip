@@ -23,6 +23,10 @@
 //
 // Cosine: REDFT10 (DCT-II) and REDFT01 (DCT-III) through one complex FFT of length N
 // (Makhoul's even/odd reordering), in LDS, batched one transform per workgroup.
+//
+// Frames and Cosine transforms above kMaxN = 8192 points (to 2^18, hz_stft_create_long /
+// hz_dct_create) do not fit in LDS: step 2 and the slot transforms then run as the column and
+// row launches of hz_fft_long.h through a device workspace; steps 1 and 3 are unchanged.
 #include <algorithm>
 #include <climits>
 #include <cstdlib>
@@ -33,6 +37,7 @@
 
 #include "hz_common.h"
 #include "hz_fft.h"
+#include "hz_fft_long.h"
 
 // Experiment builds only (-DHZ_STFT_ABLATE=mask; wrong results): 1 skip the processor,
 // 2 skip the inverse FFT, 4 skip the forward FFT, 8 skip the ring store, 16 twiddles = tw[0].
@@ -45,8 +50,12 @@ namespace {
 constexpr int kThreads = 1024;       // DCT workgroups: one radix-4 butterfly per thread at N = 4096
 constexpr int kFrameThreads = 512;   // STFT frame workgroups (N/8 threads at N = 4096, N/16 at 8192)
 constexpr int kMaxN = 8192;          // complex FP64 frame fully resident in LDS (128 KB)
+constexpr int kMaxLongN = 1 << hzl::kMaxLg;   // multi-pass frames through a device workspace (hz_fft_long.h)
 constexpr long kChunkMax = 1L << 20;          // samples per internal block: one frame launch each
 constexpr size_t kRingBytes = 128u << 20;     // frame-ring budget that caps the block below kChunkMax
+// long frames (N > kMaxN): 2 laps + 2 live frames alone are 136 MB at (262144, 16), so the budget
+// is larger and the block may shrink to one frame length
+constexpr size_t kLongRingBytes = 384u << 20;
 
 struct StftArgs {
     const double* hr;     // history: hr[k] = Re input at time T0 - (N-1) + k, k < N-1
@@ -1185,6 +1194,11 @@ struct hz_stft {
     std::vector<char> s_reading, s_writing;
     std::vector<double> h_win;
     hz::DevBuf<double2> d_slot;  // [2][N] device scratch
+    // long frames (N > kMaxN, hz_fft_long.h): N = 2^lg1 2^lg2, sub-transform twiddles, the
+    // inter-pass workspace [frames of a block][N] and the gates' per-workgroup partial sums
+    int lg1 = 0, lg2 = 0;
+    hz::DevBuf<double2> d_tw1, d_tw2, d_ws;
+    hz::DevBuf<double> d_part;
 };
 
 namespace {
@@ -1256,10 +1270,69 @@ void launch_pairs(hz_stft* h, const StftArgs& a, long nf) {
 
 // real input and a magnitude gate: two frames per transform (stft_pair_kernel)
 bool pair_launch(const hz_stft* h, const StftArgs& a) {
-    return h->pair_ok && !a.hi && h->N >= 16 && (h->proc == HZ_PROC_STATIC_GATE || h->proc == HZ_PROC_GATE_KEEP);
+    return h->pair_ok && !a.hi && h->N >= 16 && h->N <= kMaxN && (h->proc == HZ_PROC_STATIC_GATE || h->proc == HZ_PROC_GATE_KEEP);
+}
+
+hzl::Args long_args(const hz_stft* h, const StftArgs& a) {
+    hzl::Args l = {};
+    l.hr = a.hr;
+    l.hi = a.hi;
+    l.inr = a.inr;
+    l.ini = a.ini;
+    l.win = a.win;
+    l.fo = a.fo;
+    l.csrc = a.spec;
+    l.cdst = a.spec;
+    l.ws = h->d_ws;
+    l.part = h->d_part;
+    l.tw1 = h->d_tw1;
+    l.tw2 = h->d_tw2;
+    l.twN = h->d_tw;
+    l.f_lo = a.f_lo;
+    l.T0 = a.T0;
+    l.lg = h->lg;
+    l.lg1 = h->lg1;
+    l.lg2 = h->lg2;
+    l.laps = a.laps;
+    l.stride = a.stride;
+    l.R = a.R;
+    l.p0 = a.p0;
+    l.p1 = a.p1;
+    return l;
+}
+
+// launch_frames<PROC, MODE> for N > kMaxN: every launch covers all nf frames of the block
+// (grid = frames x tiles); three launches fused (identity, Hilbert), four with a gate, two each
+// for the forward-only (mode 1) and inverse-only (mode 2) halves of the host-processor path
+int long_frames(hz_stft* h, const StftArgs& a, long nf, int mode) {
+    HZ_TRY(h->d_ws.reserve((size_t)nf * h->N));
+    HZ_TRY(h->d_part.reserve((size_t)nf * 2 * ((size_t)1 << h->lg1) / hzl::kRows));
+    const hzl::Args l = long_args(h, a);
+    hipStream_t s = h->stream;
+    if (mode != 2) hzl::col_fwd<hzl::kIoStft>(l, nf, s);
+    if (mode == 1) {
+        hzl::row<HZ_PROC_IDENTITY, hzl::kRowFwdOut, false>(l, nf, s);
+        HZ_TRY_HIP(hipGetLastError());
+        return HZ_OK;
+    }
+    if (mode == 2) hzl::row<HZ_PROC_IDENTITY, hzl::kRowInInv, false>(l, nf, s);
+    else if (h->proc == HZ_PROC_STATIC_GATE) {
+        hzl::row<HZ_PROC_STATIC_GATE, hzl::kRowFwdGate, false>(l, nf, s);
+        hzl::row<HZ_PROC_STATIC_GATE, hzl::kRowGateInv, false>(l, nf, s);
+    } else if (h->proc == HZ_PROC_GATE_KEEP) {
+        hzl::row<HZ_PROC_GATE_KEEP, hzl::kRowFwdGate, false>(l, nf, s);
+        hzl::row<HZ_PROC_GATE_KEEP, hzl::kRowGateInv, false>(l, nf, s);
+    } else if (h->proc == HZ_PROC_HILBERT)
+        hzl::row<HZ_PROC_HILBERT, hzl::kRowFused, false>(l, nf, s);
+    else
+        hzl::row<HZ_PROC_IDENTITY, hzl::kRowFused, false>(l, nf, s);
+    hzl::col_inv<hzl::kIoStft>(l, nf, s);
+    HZ_TRY_HIP(hipGetLastError());
+    return HZ_OK;
 }
 
 int frames_fused(hz_stft* h, const StftArgs& a, long nf) {
+    if (h->N > kMaxN) return long_frames(h, a, nf, 0);
     if (pair_launch(h, a)) {
         if (h->proc == HZ_PROC_STATIC_GATE) launch_pairs<HZ_PROC_STATIC_GATE>(h, a, nf);
         else launch_pairs<HZ_PROC_GATE_KEEP>(h, a, nf);
@@ -1357,7 +1430,8 @@ int stft_block(hz_stft* h, const double* d_re, const double* d_im, double* d_ore
             } else {
                 HZ_TRY(h->d_spec.reserve((size_t)nf * N));
                 a.spec = h->d_spec;
-                launch_frames<HZ_PROC_IDENTITY, 1>(h, a, nf);
+                if (N > kMaxN) HZ_TRY(long_frames(h, a, nf, 1));
+                else launch_frames<HZ_PROC_IDENTITY, 1>(h, a, nf);
                 HZ_TRY_HIP(hipGetLastError());
                 h->h_spec.resize((size_t)nf * N);
                 HZ_TRY_HIP(hipMemcpyAsync(h->h_spec.data(), h->d_spec, sizeof(double2) * (size_t)nf * N,
@@ -1372,7 +1446,8 @@ int stft_block(hz_stft* h, const double* d_re, const double* d_im, double* d_ore
                 }
                 HZ_TRY_HIP(hipMemcpyAsync(h->d_spec, h->h_spec.data(), sizeof(double2) * (size_t)nf * N,
                                           hipMemcpyHostToDevice, h->stream));
-                launch_frames<HZ_PROC_IDENTITY, 2>(h, a, nf);
+                if (N > kMaxN) HZ_TRY(long_frames(h, a, nf, 2));
+                else launch_frames<HZ_PROC_IDENTITY, 2>(h, a, nf);
                 HZ_TRY_HIP(hipGetLastError());
             }
         }
@@ -1442,12 +1517,15 @@ int stft_run(hz_stft* h, const double* d_re, const double* d_im, double* d_ore, 
 
 }  // namespace
 
-extern "C" {
+namespace {
 
-int hz_stft_create(int N, int laps, int window, int proc, double p0, double p1, int device, hz_stft** out) {
-    if (!out || !pow2(N) || N > kMaxN || laps <= 0 || laps > N || (window != HZ_WIN_HALFHANN && window != HZ_WIN_HANN) ||
+// hz_stft_create (max_n = kMaxN) and hz_stft_create_long (kMaxLongN): one construction; N decides
+// the engine, so a long handle at N <= kMaxN is the LDS-resident engine, bit for bit
+int stft_create(const char* who, int max_n, int N, int laps, int window, int proc, double p0, double p1, int device,
+                hz_stft** out) {
+    if (!out || !pow2(N) || N > max_n || laps <= 0 || laps > N || (window != HZ_WIN_HALFHANN && window != HZ_WIN_HANN) ||
         proc < HZ_PROC_IDENTITY || proc > HZ_PROC_HOST) {
-        hz::set_error("hz_stft_create: invalid arguments (N must be a power of two in [4, %d])", kMaxN);
+        hz::set_error("%s: invalid arguments (N must be a power of two in [4, %d])", who, max_n);
         return HZ_E_INVALID;
     }
     *out = nullptr;
@@ -1467,9 +1545,14 @@ int hz_stft_create(int N, int laps, int window, int proc, double p0, double p1, 
     const long P = 2L * N - 1;
     auto ring = [&](long c) { return (c + P - 1) / P * 2 * laps + 2 * laps + 2; };
     h->chunk = kChunkMax;
-    while (h->chunk > 4L * N && (size_t)ring(h->chunk) * N * sizeof(double2) > kRingBytes) h->chunk >>= 1;
+    if (N <= kMaxN)
+        while (h->chunk > 4L * N && (size_t)ring(h->chunk) * N * sizeof(double2) > kRingBytes) h->chunk >>= 1;
+    else
+        while (h->chunk > (long)N && (size_t)ring(h->chunk) * N * sizeof(double2) > kLongRingBytes) h->chunk >>= 1;
     h->R = (int)ring(h->chunk);
-    h->h_out.assign((size_t)2 * laps * N, make_double2(0.0, 0.0));
+    // the host processor's per-slot out buffers (128 MB at (262144, 16)): long handles get them
+    // with the processor
+    if (N <= kMaxN || proc == HZ_PROC_HOST) h->h_out.assign((size_t)2 * laps * N, make_double2(0.0, 0.0));
     std::vector<double> win(N);
     for (int k = 0; k < N; ++k) {   // src/wave.h:148-149 with the truncated PI, in double
         const double p = k / (double)N;
@@ -1504,8 +1587,17 @@ int hz_stft_create(int N, int laps, int window, int proc, double p0, double p1, 
     ok = ok && hipMemcpy(h->d_win, win.data(), sizeof(double) * N, hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && hipMemcpy(h->d_tw, twx.data(), sizeof(double2) * twx.size(), hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && hipMemset(h->d_fo, 0, sizeof(double2) * (size_t)h->R * N) == hipSuccess;
+    if (N > kMaxN) {
+        hzl::split_lg(h->lg, h->lg1, h->lg2);
+        const std::vector<double2> t1 = twiddles(1 << h->lg1), t2 = twiddles(1 << h->lg2);
+        ok = ok && h->d_tw1.reserve(t1.size()) == HZ_OK && h->d_tw2.reserve(t2.size()) == HZ_OK;
+        ok = ok && hipMemcpy(h->d_tw1, t1.data(), sizeof(double2) * t1.size(), hipMemcpyHostToDevice) == hipSuccess;
+        ok = ok && hipMemcpy(h->d_tw2, t2.data(), sizeof(double2) * t2.size(), hipMemcpyHostToDevice) == hipSuccess;
+        ok = ok && h->d_ws.reserve((size_t)N) == HZ_OK;
+        hzl::init_attrs();
+    }
     if (!ok) {
-        hz::set_error("hz_stft_create: device allocation failed");
+        hz::set_error("%s: device allocation failed", who);
         if (h->stream) (void)hipStreamDestroy(h->stream);
         delete h;
         return HZ_E_ALLOC;
@@ -1531,6 +1623,18 @@ int hz_stft_create(int N, int laps, int window, int proc, double p0, double p1, 
     return HZ_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int hz_stft_create(int N, int laps, int window, int proc, double p0, double p1, int device, hz_stft** out) {
+    return stft_create("hz_stft_create", kMaxN, N, laps, window, proc, p0, p1, device, out);
+}
+
+int hz_stft_create_long(int N, int laps, int window, int proc, double p0, double p1, int device, hz_stft** out) {
+    return stft_create("hz_stft_create_long", kMaxLongN, N, laps, window, proc, p0, p1, device, out);
+}
+
 int hz_stft_destroy(hz_stft* h) {
     if (!h) return HZ_OK;
     (void)hipSetDevice(h->device);
@@ -1548,6 +1652,7 @@ int hz_stft_set_processor(hz_stft* h, hz_stft_proc fn) {
     }
     h->host_proc = fn;
     h->proc = HZ_PROC_HOST;
+    if (h->h_out.empty()) h->h_out.assign((size_t)2 * h->laps * h->N, make_double2(0.0, 0.0));
     return HZ_OK;
 }
 
@@ -1625,6 +1730,22 @@ int slot_check(hz_stft* h, int i) {
 int slot_transform(hz_stft* h, const double2* src, double2* dst, bool inverse) {
     const int N = h->N;
     HZ_TRY_HIP(hipMemcpyAsync(h->d_slot, src, sizeof(double2) * N, hipMemcpyHostToDevice, h->stream));
+    if (N > kMaxN) {   // one frame through the two passes of hz_fft_long.h, FFTW order in and out
+        hzl::Args l = long_args(h, StftArgs{});
+        l.csrc = h->d_slot;
+        l.cdst = h->d_slot + N;
+        if (inverse) {
+            hzl::row<HZ_PROC_IDENTITY, hzl::kRowInInv, false>(l, 1, h->stream);
+            hzl::col_inv<hzl::kIoComplex>(l, 1, h->stream);
+        } else {
+            hzl::col_fwd<hzl::kIoComplex>(l, 1, h->stream);
+            hzl::row<HZ_PROC_IDENTITY, hzl::kRowFwdOut, false>(l, 1, h->stream);
+        }
+        HZ_TRY_HIP(hipGetLastError());
+        HZ_TRY_HIP(hipMemcpyAsync(dst, h->d_slot + N, sizeof(double2) * N, hipMemcpyDeviceToHost, h->stream));
+        HZ_TRY_HIP(hipStreamSynchronize(h->stream));
+        return HZ_OK;
+    }
     auto launch = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(1), dim3(frame_threads(N)), frame_lds(N), h->stream, (const double2*)h->d_slot,
                            h->d_slot + N, N, h->lg, (const double2*)h->d_tw);
@@ -1765,6 +1886,10 @@ int hz_stft_set_frame_shard(hz_stft* h, int rank, int world, long block) {
         hz::set_error("hz_stft_set_frame_shard: a host processor sees every frame in order (replicas only)");
         return HZ_E_UNSUPPORTED;
     }
+    if (h->N > kMaxN && world > 1) {
+        hz::set_error("hz_stft_set_frame_shard: time-range shards are not built for frames above %d points", kMaxN);
+        return HZ_E_UNSUPPORTED;
+    }
     h->sh_rank = rank;
     h->sh_world = world;
     h->sh_block = block;
@@ -1843,11 +1968,39 @@ struct hz_dct {
     hz::DevBuf<double> d_a, d_b;
     hz::DevBuf<double2> d_tw, d_rot;
     hipStream_t stream = nullptr;
+    // N > kMaxN: the two passes of hz_fft_long.h through a workspace [batch][N]
+    int lg1 = 0, lg2 = 0;
+    hz::DevBuf<double2> d_tw1, d_tw2, d_ws;
 };
 
 namespace {
 
 int dct_launch(hz_dct* h, const double* d_x, double* d_y, int batch, int kind) {
+    if (h->N > kMaxN) {
+        // Makhoul's reorder in the first pass's load, the rotation in the last pass's store
+        // (REDFT10); REDFT01 mirrors it
+        HZ_TRY(h->d_ws.reserve((size_t)batch * h->N));
+        hzl::Args l = {};
+        l.rsrc = d_x;
+        l.rdst = d_y;
+        l.ws = h->d_ws;
+        l.tw1 = h->d_tw1;
+        l.tw2 = h->d_tw2;
+        l.twN = h->d_tw;
+        l.rot = h->d_rot;
+        l.lg = h->lg;
+        l.lg1 = h->lg1;
+        l.lg2 = h->lg2;
+        if (kind == 10) {
+            hzl::col_fwd<hzl::kIoDct>(l, batch, h->stream);
+            hzl::row<HZ_PROC_IDENTITY, hzl::kRowFwdOut, true>(l, batch, h->stream);
+        } else {
+            hzl::row<HZ_PROC_IDENTITY, hzl::kRowInInv, true>(l, batch, h->stream);
+            hzl::col_inv<hzl::kIoDct>(l, batch, h->stream);
+        }
+        HZ_TRY_HIP(hipGetLastError());
+        return HZ_OK;
+    }
     const size_t lds = sizeof(double) * 2 * (size_t)h->N;
     if (kind == 10)
         hipLaunchKernelGGL(dct2_kernel, dim3((unsigned)batch), dim3(kThreads), lds, h->stream, d_x, d_y, h->N, h->lg,
@@ -1864,8 +2017,8 @@ int dct_launch(hz_dct* h, const double* d_x, double* d_y, int batch, int kind) {
 extern "C" {
 
 int hz_dct_create(int N, int device, hz_dct** out) {
-    if (!out || !pow2(N) || N > kMaxN) {
-        hz::set_error("hz_dct_create: N must be a power of two in [4, %d]", kMaxN);
+    if (!out || !pow2(N) || N > kMaxLongN) {
+        hz::set_error("hz_dct_create: N must be a power of two in [4, %d]", kMaxLongN);
         return HZ_E_INVALID;
     }
     *out = nullptr;
@@ -1888,6 +2041,15 @@ int hz_dct_create(int N, int device, hz_dct** out) {
     ok = ok && h->d_tw.reserve(N / 2) == HZ_OK && h->d_rot.reserve(N) == HZ_OK;
     ok = ok && hipMemcpy(h->d_tw, tw.data(), sizeof(double2) * (N / 2), hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && hipMemcpy(h->d_rot, rot.data(), sizeof(double2) * N, hipMemcpyHostToDevice) == hipSuccess;
+    if (N > kMaxN) {
+        hzl::split_lg(h->lg, h->lg1, h->lg2);
+        const std::vector<double2> t1 = twiddles(1 << h->lg1), t2 = twiddles(1 << h->lg2);
+        ok = ok && h->d_tw1.reserve(t1.size()) == HZ_OK && h->d_tw2.reserve(t2.size()) == HZ_OK;
+        ok = ok && hipMemcpy(h->d_tw1, t1.data(), sizeof(double2) * t1.size(), hipMemcpyHostToDevice) == hipSuccess;
+        ok = ok && hipMemcpy(h->d_tw2, t2.data(), sizeof(double2) * t2.size(), hipMemcpyHostToDevice) == hipSuccess;
+        ok = ok && h->d_ws.reserve((size_t)N) == HZ_OK;
+        hzl::init_attrs();
+    }
     if (!ok) {
         hz::set_error("hz_dct_create: allocation failed");
         if (h->stream) (void)hipStreamDestroy(h->stream);

@@ -4,6 +4,11 @@ Fourier(processor, N, laps)   src/fourier.h:50-194 (halfhann windows)
 StaticSTFT(N, laps)           src/staticSTFT.h:10-177 (hann windows, built-in gate)
 Cosine(N)                     src/fourier.h:197-234 (REDFT10 forward, REDFT01 backward)
 
+N is a power of two up to 8192; long_frames=True (hz_stft_create_long) allows up to 262144, and
+builds the same engine below the limit.  Cosine takes N up to 262144 as it is.  params=(p0, p1)
+replaces a built-in gate's constants: Fourier(PROC_GATE_KEEP, N, laps, params=(10.0, 0.0)) keeps
+the bins with |X|^2 > 10 average^2.
+
 process_block(re, im) == n x { write(re[t], im[t]); read(&re_out, &im_out); }.
 A processor is a built-in id (PROC_*) or a Python callable f(inp, out) over complex128
 arrays of length N, run per frame in frame order (host path).
@@ -24,12 +29,13 @@ PROC_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double))
 
 class Fourier:
     def __init__(self, processor=PROC_IDENTITY, N: int = 4096, laps: int = 4, window: int = WIN_HALFHANN,
-                 device: int = 0):
+                 device: int = 0, *, long_frames: bool = False, params=None):
         lib = load()
         builtin = processor if isinstance(processor, int) else PROC_HOST
-        p0, p1 = _PARAMS.get(builtin, (0.0, 0.0))
+        p0, p1 = _PARAMS.get(builtin, (0.0, 0.0)) if params is None else (float(params[0]), float(params[1]))
         h = C.c_void_p()
-        check(lib.hz_stft_create(N, laps, window, builtin, p0, p1, device, C.byref(h)))
+        create = lib.hz_stft_create_long if long_frames else lib.hz_stft_create
+        check(create(N, laps, window, builtin, p0, p1, device, C.byref(h)))
         self._h, self._lib, self.N, self.laps = h, lib, N, laps
         self._cb = None
         if builtin == PROC_HOST:
@@ -122,8 +128,8 @@ def frames_before(N: int, laps: int, samples: int) -> int:
 
 
 class StaticSTFT(Fourier):
-    def __init__(self, N: int = 4096, laps: int = 4, device: int = 0):
-        super().__init__(PROC_STATIC_GATE, N, laps, WIN_HANN, device)
+    def __init__(self, N: int = 4096, laps: int = 4, device: int = 0, *, long_frames: bool = False):
+        super().__init__(PROC_STATIC_GATE, N, laps, WIN_HANN, device, long_frames=long_frames)
 
 
 class Cosine:

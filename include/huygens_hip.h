@@ -491,6 +491,12 @@ int hz_bowl_fill_delaybank(hz_bowl* bowl, float* d_buffer, hz_dly* bank, void* d
 typedef int (*hz_stft_proc)(const double* in, double* out);
 typedef struct hz_stft hz_stft;
 int hz_stft_create(int N, int laps, int window, int proc, double p0, double p1, int device, hz_stft** out);
+/* The same object for N a power of two in [4, 262144].  Up to 8192 it is exactly what
+ * hz_stft_create builds (the LDS-resident frame engine, the same bits).  Above, a frame runs as
+ * a four-step transform through a device workspace (3 launches per internal block, 4 with a
+ * gate); every call of this section works on such a handle except time-range shards:
+ * hz_stft_set_frame_shard with world > 1 returns HZ_E_UNSUPPORTED. */
+int hz_stft_create_long(int N, int laps, int window, int proc, double p0, double p1, int device, hz_stft** out);
 int hz_stft_destroy(hz_stft* h);
 int hz_stft_set_processor(hz_stft* h, hz_stft_proc fn);
 int hz_stft_process_block(hz_stft* h, const double* re, const double* im, double* out_re, double* out_im, size_t n);
@@ -532,7 +538,8 @@ int hz_stft_profile_read(hz_stft* h, double* frame_ms, double* ola_ms, long* blo
 /* ---- Cosine (src/fourier.h:197-234): Cosine(int N, double** in, double** out) ----
  * forward = FFTW REDFT10 in -> out (DCT-II, unnormalised), backward = REDFT01 out -> in
  * (DCT-III); the round trip is 2N x identity.  The buffers are pinned host memory owned
- * by the handle.  N a power of two in [4, 8192]. */
+ * by the handle.  N a power of two in [4, 262144] (above 8192: two launches per transform
+ * through a device workspace). */
 typedef struct hz_dct hz_dct;
 int hz_dct_create(int N, int device, hz_dct** out);
 int hz_dct_destroy(hz_dct* h);

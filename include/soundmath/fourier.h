@@ -8,6 +8,8 @@
 //   by blocks: process_block() == n x {write(x_t); read(&y_t)} on the GPU frame engine.
 // A processor is the reference's int(*)(const complex<double>*, complex<double>*), run on the
 // host per frame in frame order, or a built-in device processor (HZ_PROC_*).
+// N is a power of two up to 262144, as the reference's programs use (hz_stft_create_long; up to
+// 8192 a frame stays in LDS, above it runs as a four-step transform).
 #pragma once
 
 #include "hz.h"
@@ -38,7 +40,7 @@ protected:
         const double p0 = proc == HZ_PROC_STATIC_GATE ? 100.0 : (proc == HZ_PROC_GATE_KEEP ? 625.0 : 0.0);
         const double p1 = proc == HZ_PROC_STATIC_GATE ? 0.1 : 0.0;
         hz_stft* h = nullptr;
-        detail::check(hz_stft_create(N, laps, window, proc, p0, p1, device, &h), "Fourier");
+        detail::check(hz_stft_create_long(N, laps, window, proc, p0, p1, device, &h), "Fourier");
         h_ = decltype(h_)(h);
         if (fn)   // complex<double>* and double* (interleaved) are layout-compatible
             detail::check(hz_stft_set_processor(h, reinterpret_cast<hz_stft_proc>(fn)), "Fourier");

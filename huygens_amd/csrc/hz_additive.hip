@@ -317,6 +317,7 @@ long double mtofl(long double m) { return 440.0L * powl(2.0L, (m - 69) / 12); }
 // shared engine: V voices x OL local overtones (overtones [o0, o0 + OL) of O)
 // ---------------------------------------------------------------------------
 struct PhaseBank {
+    hz::Stream stream;
     int V = 1, O = 1, o0 = 0, OL = 1, device = 0;
     double s = 0;      // oscillator stiffness
     double a = 0;      // envelope smoothing (Additive attack); 0 for Sinusoids
@@ -334,11 +335,8 @@ struct PhaseBank {
     std::vector<char> dirty;     // per voice: records need rebuilding
     std::vector<Task> tasks;
     int target_groups = 256;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
     bool prof = false;
-    std::vector<hipEvent_t> ev;
-    size_t ev_used = 0;
+    hz::ProfEvents ev;
     long launches = 0;
     // Per-sample calls (operator() / tick(): fills shorter than kLookMin) are served from a
     // speculative block: the next kLook samples rendered at once from a snapshot of the state
@@ -374,8 +372,7 @@ struct PhaseBank {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
             target_groups = prop.multiProcessorCount;
-        HZ_TRY_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        own_stream = true;
+        HZ_TRY(stream.create());
         HZ_TRY(d_rec.reserve(P * PRec::SIZE));
         HZ_TRY(d_phi.reserve(P));
         HZ_TRY(d_f.reserve(P));
@@ -388,11 +385,9 @@ struct PhaseBank {
         return HZ_OK;
     }
 
-    void release() {
+    void release() {   // quiet, before the handle is deleted
         (void)hipSetDevice(device);
-        if (stream) (void)hipStreamSynchronize(stream);
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-        if (own_stream && stream) (void)hipStreamDestroy(stream);
+        (void)stream.sync();
     }
 
     // render n samples into d_out (device), then advance all state
@@ -438,14 +433,7 @@ struct PhaseBank {
 
         hipEvent_t* e = nullptr;
         if (prof) {
-            if (ev_used + 2 > ev.size())
-                for (int q = 0; q < 128; ++q) {
-                    hipEvent_t ne;
-                    HZ_TRY_HIP(hz::prof_event_create(&ne));
-                    ev.push_back(ne);
-                }
-            e = &ev[ev_used];
-            ev_used += 2;
+            HZ_TRY(ev.take(2, &e));
             HZ_TRY_HIP(hipEventRecord(e[0], stream));
         }
         if (ntasks == 0) {
@@ -604,20 +592,14 @@ struct hz_add : hz::MinNotes {   // the note layer: position covers all overtone
         static constexpr size_t kMaxRowBytes = (size_t)32 << 20;
         hz::DevBuf<double> d_x, d_v, d_eq, d_guide, d_c, d_rows, d_amp, d_partial;
         std::vector<double> amp;   // [n + 1][V] envelope rows of the piece being rendered
-        std::vector<hipEvent_t> ev;   // profile: 3 per piece (start, physics done, audio done)
-        size_t ev_used = 0;
+        hz::ProfEvents ev;   // profile: 3 per piece (start, physics done, audio done)
     } phys;
 };
 
 namespace {
 
 int add_check(hz_add* h) {
-    if (!h) {
-        hz::set_error("null hz_add handle");
-        return HZ_E_INVALID;
-    }
-    HZ_TRY_HIP(hipSetDevice(h->bank.device));
-    return HZ_OK;
+    return hz::check_handle(h ? &h->bank : nullptr, "hz_add");   // (the bank has the device)
 }
 
 // Additive::tick's freqmod(mtof(particle position)) for the local overtones of voice v
@@ -773,14 +755,7 @@ int phys_render(hz_add* h, double* d_dst, long n) {
         HZ_TRY(phys_upload_call(h, m + 1));
         hipEvent_t* e = nullptr;
         if (b.prof) {
-            if (ph.ev_used + 3 > ph.ev.size())
-                for (int q = 0; q < 96; ++q) {
-                    hipEvent_t ne;
-                    HZ_TRY_HIP(hz::prof_event_create(&ne));
-                    ph.ev.push_back(ne);
-                }
-            e = &ph.ev[ph.ev_used];
-            ph.ev_used += 3;
+            HZ_TRY(ph.ev.take(3, &e));
             HZ_TRY_HIP(hipEventRecord(e[0], b.stream));
         }
         HZ_TRY(phys_steps(h, steps));
@@ -817,8 +792,7 @@ int hz_add_create_shard(int voices, int overtones, int o_begin, int o_count, dou
     h->norm = decay != 1 ? (1 - std::pow(decay, overtones)) / (1 - decay) : overtones;
     int rc = h->bank.init(voices, overtones, o_begin, o_count, hz::relaxation(0.0001), hz::relaxation(k), device);
     if (rc != HZ_OK) {
-        h->bank.release();
-        delete h;
+        hz_add_destroy(h);
         return rc;
     }
     for (int v = 0; v < voices; ++v)
@@ -837,7 +811,6 @@ int hz_add_create(int voices, int overtones, double decay, double harmonicity, d
 int hz_add_destroy(hz_add* h) {
     if (!h) return HZ_OK;
     h->bank.release();
-    for (hipEvent_t e : h->phys.ev) (void)hipEventDestroy(e);
     delete h;
     return HZ_OK;
 }
@@ -919,16 +892,7 @@ int hz_add_lookahead_info(hz_add* h, long* blocks, long* rollbacks, long* block_
 int hz_add_set_stream(hz_add* h, void* s) {
     HZ_TRY(add_check(h));
     HZ_TRY(h->bank.settle());
-    HZ_TRY_HIP(hipStreamSynchronize(h->bank.stream));
-    if (h->bank.own_stream) HZ_TRY_HIP(hipStreamDestroy(h->bank.stream));
-    if (s) {
-        h->bank.stream = (hipStream_t)s;
-        h->bank.own_stream = false;
-    } else {
-        HZ_TRY_HIP(hipStreamCreateWithFlags(&h->bank.stream, hipStreamNonBlocking));
-        h->bank.own_stream = true;
-    }
-    return HZ_OK;
+    return h->bank.stream.rebind(s, hz::NullMeans::Private);
 }
 
 int hz_add_set_target_groups(hz_add* h, int groups) {
@@ -941,9 +905,9 @@ int hz_add_profile(hz_add* h, int enable) {
     HZ_TRY(add_check(h));
     HZ_TRY_HIP(hipStreamSynchronize(h->bank.stream));
     h->bank.prof = enable != 0;
-    h->bank.ev_used = 0;
+    h->bank.ev.rewind();
     h->bank.launches = 0;
-    h->phys.ev_used = 0;
+    h->phys.ev.rewind();
     return HZ_OK;
 }
 
@@ -951,11 +915,7 @@ int hz_add_profile_read(hz_add* h, double* ms, long* launches) {
     HZ_TRY(add_check(h));
     HZ_TRY_HIP(hipStreamSynchronize(h->bank.stream));
     double m = 0;
-    for (size_t i = 0; i + 2 <= h->bank.ev_used; i += 2) {
-        float x = 0;
-        HZ_TRY_HIP(hipEventElapsedTime(&x, h->bank.ev[i], h->bank.ev[i + 1]));
-        m += x;
-    }
+    HZ_TRY(h->bank.ev.elapsed(2, 0, 1, &m));   // (no rewind: a read keeps the counters)
     if (ms) *ms = m;
     if (launches) *launches = h->bank.launches;
     return HZ_OK;
@@ -1053,13 +1013,8 @@ int hz_add_physics_profile_read(hz_add* h, double* physics_ms, double* audio_ms)
     HZ_TRY(add_check(h));
     HZ_TRY_HIP(hipStreamSynchronize(h->bank.stream));
     double p = 0, a = 0;
-    for (size_t i = 0; i + 3 <= h->phys.ev_used; i += 3) {
-        float x = 0;
-        HZ_TRY_HIP(hipEventElapsedTime(&x, h->phys.ev[i], h->phys.ev[i + 1]));
-        p += x;
-        HZ_TRY_HIP(hipEventElapsedTime(&x, h->phys.ev[i + 1], h->phys.ev[i + 2]));
-        a += x;
-    }
+    HZ_TRY(h->phys.ev.elapsed(3, 0, 1, &p));   // (no rewind here either)
+    HZ_TRY(h->phys.ev.elapsed(3, 1, 2, &a));
     if (physics_ms) *physics_ms = p;
     if (audio_ms) *audio_ms = a;
     return HZ_OK;
@@ -1146,8 +1101,7 @@ int hz_sin_create(double fundamental, int overtones, double decay, double harmon
     // Synth(form, fundamental * pow(i+1, harmonicity)) with the default k = 2/SR (sinusoids.h:23-27)
     int rc = h->bank.init(1, overtones, 0, overtones, hz::relaxation(2.0 / hz::kSR), 0.0, device);
     if (rc != HZ_OK) {
-        h->bank.release();
-        delete h;
+        hz_sin_destroy(h);
         return rc;
     }
     h->bank.act[0] = 1.0;
@@ -1158,7 +1112,11 @@ int hz_sin_create(double fundamental, int overtones, double decay, double harmon
     h->bank.c_first = h->bank.c;
     // oscillators start at their target frequency, phase 0 (oscillator.h:16-24)
     std::vector<double> f0(h->bank.ft);
-    HZ_TRY_HIP(hipMemcpy(h->bank.d_f, f0.data(), sizeof(double) * overtones, hipMemcpyHostToDevice));
+    if (hipMemcpy(h->bank.d_f, f0.data(), sizeof(double) * overtones, hipMemcpyHostToDevice) != hipSuccess) {
+        hz::set_error("hz_sin_create: hipMemcpy failed");
+        hz_sin_destroy(h);
+        return HZ_E_HIP;
+    }
     *out = h;
     return HZ_OK;
 }

@@ -435,17 +435,15 @@ void build_brec(double f, double amp, double d, bool is_float, double* rec) {
 }  // namespace
 
 struct hz_bowl {
+    hz::Stream stream;
     int M = 0, device = 0, is_float = 0;
     double n0 = 0;  // phase counter (T) at the next call
     hz::DevBuf<double> d_rec, d_partial;
     hz::DevBuf<char> d_chain;   // (float Bowls) [M] float4 {f, d, a, 0} then [M] double decay steps
     hz::DevBuf<char> d_out;     // doubles or floats (bytes)
     int target_groups = 256;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
     bool prof = false;
-    std::vector<hipEvent_t> ev;
-    size_t ev_used = 0;
+    hz::ProfEvents ev;
     long launches = 0;
     // per-sample calls (renders shorter than kLookMin: the drop-in's operator() / tick()) come
     // from a speculative block of kLook samples rendered at once; the state is the phase counter
@@ -459,12 +457,7 @@ struct hz_bowl {
 namespace {
 
 int bowl_check(hz_bowl* h) {
-    if (!h) {
-        hz::set_error("null hz_bowl handle");
-        return HZ_E_INVALID;
-    }
-    HZ_TRY_HIP(hipSetDevice(h->device));
-    return HZ_OK;
+    return hz::check_handle(h, "hz_bowl");
 }
 
 // out_kind: 0 = float samples (fill), 1 = double samples (operator() in T's precision)
@@ -493,14 +486,7 @@ int bowl_launch(hz_bowl* h, void* d_dst, long n, int out_kind) {
     }
     hipEvent_t* e = nullptr;
     if (h->prof) {
-        if (h->ev_used + 2 > h->ev.size())
-            for (int q = 0; q < 128; ++q) {
-                hipEvent_t ne;
-                HZ_TRY_HIP(hz::prof_event_create(&ne));
-                h->ev.push_back(ne);
-            }
-        e = &h->ev[h->ev_used];
-        h->ev_used += 2;
+        HZ_TRY(h->ev.take(2, &e));
         HZ_TRY_HIP(hipEventRecord(e[0], h->stream));
     }
     BowlArgs args;
@@ -600,15 +586,13 @@ int hz_bowl_create(int overtones, const double* f, const double* a, const double
         }
         build_brec(fi, ai, di, h->is_float, &rec[(size_t)i * BRec::SIZE]);
     }
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
+    if (h->stream.create() != HZ_OK ||
         h->d_rec.reserve(rec.size()) != HZ_OK ||
         hipMemcpy(h->d_rec, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice) != hipSuccess) {
         hz::set_error("hz_bowl_create: device allocation failed");
-        if (h->stream) (void)hipStreamDestroy(h->stream);
         delete h;
         return HZ_E_ALLOC;
     }
-    h->own_stream = true;
     if (h->is_float) {   // the fused block's compact mode table (hz_bowl_fill_delaybank)
         std::vector<float> fda((size_t)overtones * 4, 0.0f);
         std::vector<double> rs((size_t)overtones);
@@ -636,9 +620,7 @@ int hz_bowl_create(int overtones, const double* f, const double* a, const double
 int hz_bowl_destroy(hz_bowl* h) {
     if (!h) return HZ_OK;
     (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+    (void)h->stream.sync();
     delete h;
     return HZ_OK;
 }
@@ -695,16 +677,7 @@ int hz_bowl_phase(hz_bowl* h, double* phase) {
 
 int hz_bowl_set_stream(hz_bowl* h, void* s) {
     HZ_TRY(bowl_check(h));
-    HZ_TRY_HIP(hipStreamSynchronize(h->stream));
-    if (h->own_stream) HZ_TRY_HIP(hipStreamDestroy(h->stream));
-    if (s) {
-        h->stream = (hipStream_t)s;
-        h->own_stream = false;
-    } else {
-        HZ_TRY_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        h->own_stream = true;
-    }
-    return HZ_OK;
+    return h->stream.rebind(s, hz::NullMeans::Private);
 }
 
 int hz_bowl_set_target_groups(hz_bowl* h, int groups) {
@@ -717,7 +690,7 @@ int hz_bowl_profile(hz_bowl* h, int enable) {
     HZ_TRY(bowl_check(h));
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     h->prof = enable != 0;
-    h->ev_used = 0;
+    h->ev.rewind();
     h->launches = 0;
     return HZ_OK;
 }
@@ -726,11 +699,7 @@ int hz_bowl_profile_read(hz_bowl* h, double* ms, long* launches) {
     HZ_TRY(bowl_check(h));
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     double m = 0;
-    for (size_t i = 0; i + 2 <= h->ev_used; i += 2) {
-        float x = 0;
-        HZ_TRY_HIP(hipEventElapsedTime(&x, h->ev[i], h->ev[i + 1]));
-        m += x;
-    }
+    HZ_TRY(h->ev.elapsed(2, 0, 1, &m));
     if (ms) *ms = m;
     if (launches) *launches = h->launches;
     return HZ_OK;
@@ -759,14 +728,7 @@ int hz_bowl_fill_delaybank(hz_bowl* h, float* d_buf, hz_dly* bank, void* d_out, 
     }
     hipEvent_t* e = nullptr;
     if (h->prof) {
-        if (h->ev_used + 2 > h->ev.size())
-            for (int q = 0; q < 128; ++q) {
-                hipEvent_t ne;
-                HZ_TRY_HIP(hz::prof_event_create(&ne));
-                h->ev.push_back(ne);
-            }
-        e = &h->ev[h->ev_used];
-        h->ev_used += 2;
+        HZ_TRY(h->ev.take(2, &e));
         HZ_TRY_HIP(hipEventRecord(e[0], h->stream));
     }
     ChainArgs a;

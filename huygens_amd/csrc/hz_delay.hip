@@ -341,6 +341,7 @@ __global__ __launch_bounds__(kThreads) void dly_tv_line_kernel(DlyTvArgs a) {
 }  // namespace
 
 struct hz_dly {
+    hz::Stream stream;
     int N = 0, S = 0, is_float = 0, device = 0;
     unsigned size = 1, origin = 0;
     std::vector<unsigned> ft, bt;   // [N][S] delay times as given
@@ -358,11 +359,8 @@ struct hz_dly {
     hz::DevBuf<unsigned> d_sft, d_sbt;
     hz::PinBuf<char> p_tvrec;
     std::vector<char> tv_back;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
     bool prof = false;
-    std::vector<hipEvent_t> ev;
-    size_t ev_used = 0;
+    hz::ProfEvents ev;
     long launches = 0;
     bool pending = false;           // block work queued on the stream since the last synchronisation
     size_t elem() const { return is_float ? sizeof(float) : sizeof(double); }
@@ -371,12 +369,7 @@ struct hz_dly {
 namespace {
 
 int dly_check(hz_dly* h) {
-    if (!h) {
-        hz::set_error("null hz_dly handle");
-        return HZ_E_INVALID;
-    }
-    HZ_TRY_HIP(hipSetDevice(h->device));
-    return HZ_OK;
+    return hz::check_handle(h, "hz_dly");
 }
 
 // c = (int)(T)d  (buffer.h:42 with the uint delay converted to T by the call in delay.h:82-83)
@@ -436,14 +429,7 @@ int dly_upload(hz_dly* h) {
 int dly_prof_begin(hz_dly* h, hipEvent_t** e) {
     *e = nullptr;
     if (!h->prof) return HZ_OK;
-    if (h->ev_used + 2 > h->ev.size())
-        for (int q = 0; q < 128; ++q) {
-            hipEvent_t ne;
-            HZ_TRY_HIP(hz::prof_event_create(&ne));
-            h->ev.push_back(ne);
-        }
-    *e = &h->ev[h->ev_used];
-    h->ev_used += 2;
+    HZ_TRY(h->ev.take(2, e));
     HZ_TRY_HIP(hipEventRecord((*e)[0], h->stream));
     return HZ_OK;
 }
@@ -753,7 +739,7 @@ int hz_dly_create(int lines, unsigned sparsity, unsigned time, int is_float, int
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
         h->target_groups = prop.multiProcessorCount;
     const size_t ring = h->elem() * (size_t)lines * h->size;
-    bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess;
+    bool ok = h->stream.create() == HZ_OK;
     ok = ok && h->d_taps.reserve((size_t)lines * 2 * sparsity) == HZ_OK;
     ok = ok && h->d_gains.reserve(h->elem() * (size_t)lines * 2 * sparsity) == HZ_OK;
     ok = ok && h->d_rx.reserve(ring) == HZ_OK && h->d_ry.reserve(ring) == HZ_OK;
@@ -762,11 +748,9 @@ int hz_dly_create(int lines, unsigned sparsity, unsigned time, int is_float, int
     ok = ok && hipStreamSynchronize(h->stream) == hipSuccess;
     if (!ok) {
         hz::set_error("hz_dly_create: device allocation failed (%zu bytes of rings)", 2 * ring);
-        if (h->stream) (void)hipStreamDestroy(h->stream);
         delete h;
         return HZ_E_ALLOC;
     }
-    h->own_stream = true;
     *out = h;
     return HZ_OK;
 }
@@ -774,9 +758,7 @@ int hz_dly_create(int lines, unsigned sparsity, unsigned time, int is_float, int
 int hz_dly_destroy(hz_dly* h) {
     if (!h) return HZ_OK;
     (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+    (void)h->stream.sync();
     delete h;
     return HZ_OK;
 }
@@ -951,11 +933,7 @@ int hz_dly_set_split(hz_dly* h, int mode) {
 
 int hz_dly_set_stream(hz_dly* h, void* stream) {
     HZ_TRY(dly_check(h));
-    HZ_TRY_HIP(hipStreamSynchronize(h->stream));
-    if (h->own_stream) HZ_TRY_HIP(hipStreamDestroy(h->stream));
-    h->stream = (hipStream_t)stream;
-    h->own_stream = false;
-    return HZ_OK;
+    return h->stream.rebind(stream, hz::NullMeans::Legacy);
 }
 
 int hz_dly_synchronize(hz_dly* h) {
@@ -974,7 +952,7 @@ int hz_dly_profile(hz_dly* h, int enable) {
     HZ_TRY(dly_check(h));
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     h->prof = enable != 0;
-    h->ev_used = 0;
+    h->ev.rewind();
     h->launches = 0;
     return HZ_OK;
 }
@@ -983,14 +961,10 @@ int hz_dly_profile_read(hz_dly* h, double* ms, long* launches) {
     HZ_TRY(dly_check(h));
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     double tot = 0.0;
-    for (size_t i = 0; i + 1 < h->ev_used; i += 2) {
-        float t = 0.f;
-        HZ_TRY_HIP(hipEventElapsedTime(&t, h->ev[i], h->ev[i + 1]));
-        tot += t;
-    }
+    HZ_TRY(h->ev.elapsed(2, 0, 1, &tot));
     if (ms) *ms = tot;
     if (launches) *launches = h->launches;
-    h->ev_used = 0;
+    h->ev.rewind();
     h->launches = 0;
     return HZ_OK;
 }

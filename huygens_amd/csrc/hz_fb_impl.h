@@ -77,6 +77,12 @@ struct hz_fb {
     long pg_gen = 0, coef_gen = 0;   // generations of the staged targets / coefficients
     long long setter_seq = 0;        // per-sample calls served when the last setter ran
     int order = 2, N = 0, N_total = 0, band_begin = 0, device = 0;
+    // the streams come before every event and buffer member, in every handle: members go in
+    // reverse order, so the buffers and events are released first and the streams last
+    hz::Stream stream;
+    // LTI launches are split in chunks whose cross-group reduce runs on a second stream,
+    // overlapped with the next chunk's mix kernel (double-buffered partial slab)
+    hz::Stream stream_red;
     double sp = 0, sg = 0;
     int rec = 8;
     // host shadows of the staged parameters
@@ -110,12 +116,9 @@ struct hz_fb {
     hz::PinBuf<double> pin_io{hipHostMallocCoherent | hipHostMallocMapped};
     long long pin_seq = 0;
     std::vector<double> h_rec;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
     // profiling
     bool prof = false;
-    std::vector<hipEvent_t> ev;  // quintuplets: start, mix start, mix end, reduce start, reduce end
-    size_t ev_used = 0;
+    hz::ProfEvents ev;  // quintuplets: start, mix start, mix end, reduce start, reduce end
     // per quintuplet: bit 1 = mix start not recorded (same point as start), bit 3 = reduce
     // start not recorded (same point as mix end); every record costs a few us of GPU time
     std::vector<unsigned char> ev_skip;
@@ -145,15 +148,12 @@ struct hz_fb {
     long mirror_clock = 0;           // samples processed (the closed form is applied lazily)
     std::vector<long> mirror_at;     // [N] mirror_clock at which pg_host[b] was last brought current
     bool converged = false;          // pg_host at the targets; cleared by every setter
-    // LTI launches are split in chunks whose cross-group reduce runs on a second stream,
-    // overlapped with the next chunk's mix kernel (double-buffered partial slab)
-    hipStream_t stream_red = nullptr;
-    std::vector<hipEvent_t> sync_ev;  // ordering events (no timing)
+    std::vector<hz::Event> sync_ev;  // stream_red's ordering events (no timing)
     hz::DevBuf<double> d_xhist_red;  // x history at the call start, for the first chunk's reduce
     // a coefficient-stream call leaves its last row staged as the coefficients; the row is
     // copied back asynchronously and turned into F/B only when they are next needed
     hz::PinBuf<double> tv_row;        // pinned host copy of the stream's last row
-    hipEvent_t tv_ev = nullptr;       // the copy's completion
+    hz::Event tv_ev;                  // the copy's completion
     bool tv_pending = false;
     int tv_kind = 0;
     double tv_param = 0;
@@ -243,8 +243,8 @@ struct hz_fb {
             hz::DevBuf<double> d_tout;   // [2][16384] tail outputs of epochs e (slot e & 1)
             long tail_launched = -1;     // last epoch whose tail convolution was issued
             bool tail_async[2] = {false, false};   // that slot's convolution ran on the side stream
-            hipStream_t side = nullptr;
-            hipEvent_t ev_main = nullptr, ev_tail[2] = {nullptr, nullptr};
+            hz::Stream side;
+            hz::Event ev_main, ev_tail[2];
             // gain transients (round 6): mix() while streaming keeps the engine.  The gain smoothers
             // share s_g, so g_n(t) = gin_n + s_g^(t - dref) D_n and the mix is
             //     out(t) = conv(h, x)(t) + s_g^(t - dref) conv(h_D, x)(t),  h_D = sum_n D_n r_n,

@@ -1336,18 +1336,18 @@ int fb_launch_lti(hz_fb* h, int gi, const double* d_in, double* d_out, long n) {
     constexpr int kMaxSlices = 32;   // GEMM band-state slices (rows of part)
     const size_t need = gemm ? (size_t)bs_tot * (n_pad_max / L) + (size_t)kMaxSlices * n_pad_max : 2 * slab;
     HZ_TRY(h->d_partial.reserve(need));
-    if (!h->stream_red) HZ_TRY_HIP(hipStreamCreateWithFlags(&h->stream_red, hipStreamNonBlocking));
+    if (!h->stream_red) HZ_TRY(h->stream_red.create());
     HZ_TRY(h->d_xhist_red.reserve(kMaxOrder));
     const long nchunks = (n + chunk - 1) / chunk;
     if ((size_t)(2 * nchunks) > h->sync_ev.size()) {
         while (h->sync_ev.size() < (size_t)(2 * nchunks)) {
-            hipEvent_t ne;
-            HZ_TRY_HIP(hipEventCreateWithFlags(&ne, hipEventDisableTiming));
-            h->sync_ev.push_back(ne);
+            hz::Event ne;
+            HZ_TRY(ne.create(hipEventDisableTiming));
+            h->sync_ev.push_back(std::move(ne));
         }
     }
-    hipEvent_t* ev_mix = h->sync_ev.data();
-    hipEvent_t* ev_red = h->sync_ev.data() + nchunks;
+    const hz::Event* ev_mix = h->sync_ev.data();
+    const hz::Event* ev_red = h->sync_ev.data() + nchunks;
     LtiKernel kmix = pick_lti(O, gi, gemm ? MODE_STATE : MODE_MIX);
     LtiKernel kend = pick_lti(O, gi, MODE_SEGEND);
     HZ_TRY(fb_set_lds_attr((const void*)kmix));
@@ -1471,7 +1471,7 @@ int fb_launch_lti(hz_fb* h, int gi, const double* d_in, double* d_out, long n) {
             HZ_TRY_HIP(hipGetLastError());
         }
         if (e && nseg > 1) HZ_TRY_HIP(hipEventRecord(e[1], h->stream));
-        else if (e) h->ev_skip[(e - h->ev.data()) / 5] |= 2;
+        else if (e) h->ev_skip[h->ev.index_of(e) / 5] |= 2;
         if (gemm && bs_pad > lti_group_rows(h->N, O)) {   // GS rows no group writes: zero
             const int gr = lti_group_rows(h->N, O);
             HZ_TRY_HIP(hipMemset2DAsync(h->d_partial + (size_t)gr * 64, sizeof(double) * bs_tot * 64, 0,
@@ -1492,7 +1492,7 @@ int fb_launch_lti(hz_fb* h, int gi, const double* d_in, double* d_out, long n) {
             // correction GEMM over band-state slices (>= 4 workgroups per CU), then the slice sum
             // + zero-state term in the reduce kernel; one stream, chunks in sequence
             double* part = h->d_partial + (size_t)bs_tot * nc_pad;
-            if (e) h->ev_skip[(e - h->ev.data()) / 5] |= 8;   // reduce start = mix end
+            if (e) h->ev_skip[h->ev.index_of(e) / 5] |= 8;   // reduce start = mix end
             int S = 1;
             HZ_TRY(fb_lti_gemm_launch(h->d_partial, set.d_kt, bs_tot, part, a.n_pad, (int)ntiles, L, h->target_groups,
                                       kMaxSlices, h->stream, &S));

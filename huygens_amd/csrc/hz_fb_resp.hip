@@ -1228,7 +1228,7 @@ int fb_launch_resp(hz_fb* h, const double* d_in, double* d_out, long n) {
     if (h->prof) {
         HZ_TRY(fb_prof_events(h, &e));
         HZ_TRY_HIP(hipEventRecord(e[0], h->stream));
-        h->ev_skip[(e - h->ev.data()) / 5] |= 2;   // no segment phase
+        h->ev_skip[h->ev.index_of(e) / 5] |= 2;   // no segment phase
     }
     RespArgs a;
     a.hist = R.d_hist[R.hcur];
@@ -1306,7 +1306,7 @@ int fb_launch_resp(hz_fb* h, const double* d_in, double* d_out, long n) {
         HZ_TRY_HIP(hipGetLastError());
         if (e && inside) {
             HZ_TRY_HIP(hipEventRecord(e[2], h->stream));
-            h->ev_skip[(e - h->ev.data()) / 5] |= 8;
+            h->ev_skip[h->ev.index_of(e) / 5] |= 8;
         }
         auto kc = so == 1 ? resp_comb_kernel<1> : so == 2 ? resp_comb_kernel<2> : resp_comb_kernel<0>;
         hipLaunchKernelGGL(kc, dim3((unsigned)(B + (chained ? st.G * st.nseg : 0))), dim3(kThreads), 0, h->stream, a,
@@ -1316,20 +1316,20 @@ int fb_launch_resp(hz_fb* h, const double* d_in, double* d_out, long n) {
         // profiling with hz_fb_profile(h, rep > 1): each (idempotent) kernel of the modal path launched rep
         // times between its events
         const int rep = e && modal ? h->prof_rep : 1;
-        if (e) h->ev_rep[(e - h->ev.data()) / 5] = (unsigned char)rep;
+        if (e) h->ev_rep[h->ev.index_of(e) / 5] = (unsigned char)rep;
         for (int r = 0; r < rep; ++r)
             hipLaunchKernelGGL(resp_fwd_kernel, dim3((unsigned)(nz + nm1)), dim3(kThreads), 0, h->stream, a, md);
         HZ_TRY_HIP(hipGetLastError());
         if (e && inside) {   // profiling: e0..e1 forward, e1..e2 MAC, e2..e4 inverse with the band states
             HZ_TRY_HIP(hipEventRecord(e[1], h->stream));
-            h->ev_skip[(e - h->ev.data()) / 5] &= (unsigned char)~2;
+            h->ev_skip[h->ev.index_of(e) / 5] &= (unsigned char)~2;
         }
         for (int r = 0; r < rep; ++r)
             launch_mac_lds(Qp, B, (const double2*)R.d_H.get(), (const double2*)R.d_Z.get(), (double2*)R.d_Y.get(), Q, h->stream);
         HZ_TRY_HIP(hipGetLastError());
         if (e && inside) {
             HZ_TRY_HIP(hipEventRecord(e[2], h->stream));
-            h->ev_skip[(e - h->ev.data()) / 5] |= 8;
+            h->ev_skip[h->ev.index_of(e) / 5] |= 8;
         }
         RespKernel ki = so == 1 ? resp_inv_kernel<1> : so == 2 ? resp_inv_kernel<2> : resp_inv_kernel<0>;
         for (int r = 0; r < rep; ++r)

@@ -1022,10 +1022,10 @@ int stream_setup(hz_fb* h) {
     if (tail) {
         HZ_TRY(S.d_tout.reserve((size_t)(2 * kE)));
         if (!S.side) {
-            HZ_TRY_HIP(hipStreamCreateWithFlags(&S.side, hipStreamNonBlocking));
-            HZ_TRY_HIP(hipEventCreateWithFlags(&S.ev_main, hipEventDisableTiming));
-            HZ_TRY_HIP(hipEventCreateWithFlags(&S.ev_tail[0], hipEventDisableTiming));
-            HZ_TRY_HIP(hipEventCreateWithFlags(&S.ev_tail[1], hipEventDisableTiming));
+            HZ_TRY(S.side.create());
+            HZ_TRY(S.ev_main.create(hipEventDisableTiming));
+            HZ_TRY(S.ev_tail[0].create(hipEventDisableTiming));
+            HZ_TRY(S.ev_tail[1].create(hipEventDisableTiming));
         }
     }
     const size_t col = (size_t)kCols * 32 * 2;   // doubles per spectrum (33 columns x 32 bins)
@@ -1292,7 +1292,7 @@ int fb_launch_stream(hz_fb* h, const double* d_in, double* d_out, long n) {
     if (h->prof) {
         HZ_TRY(fb_prof_events(h, &e));
         HZ_TRY_HIP(hipEventRecord(e[0], h->stream));
-        h->ev_skip[(e - h->ev.data()) / 5] |= 2 | 8;
+        h->ev_skip[h->ev.index_of(e) / 5] |= 2 | 8;
     }
     a.trace = trace_slot(h, S.dmode ? 1 : 0);
     if (S.dmode) {   // a gain transient: + s_g^(t - dref + 1) conv(h_D, x), its roles in the same launch
@@ -1586,11 +1586,8 @@ void fb_stream_free(hz_fb* h) {
     hz_fb::Resp::Stream& S = h->resp.st;
     (void)tail_quiet(S);
     trace_flush(h);
-    for (hipEvent_t e : {S.ev_main, S.ev_tail[0], S.ev_tail[1]})
-        if (e) (void)hipEventDestroy(e);
-    if (S.side) (void)hipStreamDestroy(S.side);
     const bool on = S.on;
-    S = hz_fb::Resp::Stream();   // (frees the buffers)
+    S = hz_fb::Resp::Stream();   // (frees the buffers, the side stream and its events)
     S.on = on;
 }
 

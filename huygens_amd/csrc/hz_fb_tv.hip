@@ -484,7 +484,7 @@ int hz_fb_process_tv_device(hz_fb* h, const double* d_in, double* d_out, size_t 
     // the coefficients last set (the stream's final row) stay staged for later calls: copied
     // back without blocking, turned into F/B by fb_tv_materialize when next needed
     HZ_TRY(h->tv_row.reserve((size_t)row));
-    if (!h->tv_ev) HZ_TRY_HIP(hipEventCreateWithFlags(&h->tv_ev, hipEventDisableTiming));
+    if (!h->tv_ev) HZ_TRY(h->tv_ev.create(hipEventDisableTiming));
     HZ_TRY_HIP(hipMemcpyAsync(h->tv_row, d_stream + ((long)n - 1) * row, sizeof(double) * row,
                               hipMemcpyDeviceToHost, h->stream));
     HZ_TRY_HIP(hipEventRecord(h->tv_ev, h->stream));

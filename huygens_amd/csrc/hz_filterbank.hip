@@ -703,19 +703,11 @@ namespace hz_fbi {
 
 // five timing events per launch (start, mix start, mix end, reduce start, reduce end)
 int fb_prof_events(hz_fb* h, hipEvent_t** e) {
-    if (h->ev_used + 5 > h->ev.size()) {
-        for (int q = 0; q < 5 * 64; ++q) {
-            hipEvent_t ne;
-            HZ_TRY_HIP(hz::prof_event_create(&ne));
-            h->ev.push_back(ne);
-        }
-    }
-    *e = &h->ev[h->ev_used];
-    h->ev_skip.resize(h->ev.size() / 5);
-    h->ev_skip[h->ev_used / 5] = 0;
-    h->ev_rep.resize(h->ev.size() / 5);
-    h->ev_rep[h->ev_used / 5] = 1;
-    h->ev_used += 5;
+    HZ_TRY(h->ev.take(5, e));
+    const size_t g = h->ev.used() / 5;   // groups taken, this one included
+    if (h->ev_skip.size() < g) h->ev_skip.resize(g), h->ev_rep.resize(g);
+    h->ev_skip[g - 1] = 0;
+    h->ev_rep[g - 1] = 1;
     return HZ_OK;
 }
 
@@ -915,11 +907,7 @@ int fb_launch(hz_fb* h, const double* d_in, double* d_out, long n) {
 }
 
 int fb_check(hz_fb* h) {
-    if (!h) {
-        hz::set_error("null hz_fb handle");
-        return HZ_E_INVALID;
-    }
-    HZ_TRY_HIP(hipSetDevice(h->device));
+    HZ_TRY(hz::check_handle(h, "hz_fb"));
     // every device-side use of the state needs it back from the per-sample engine
     return hz_fbi::fb_rt_stop(h);
 }
@@ -995,11 +983,7 @@ int hz_fb_create_shard(int order, int N_total, int band_begin, int band_count, d
         hz_fb_destroy(h);
         return code;
     };
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-        hz::set_error("hipStreamCreate failed");
-        return fail(HZ_E_HIP);
-    }
-    h->own_stream = true;
+    if (h->stream.create() != HZ_OK) return fail(HZ_E_HIP);
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
@@ -1035,14 +1019,9 @@ int hz_fb_destroy(hz_fb* h) {
     (void)hipSetDevice(h->device);
     h->rt.pending_ticks = 0;
     (void)hz_fbi::fb_rt_stop(h);   // the resident per-sample kernel leaves before the buffers go
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->stream_red) (void)hipStreamSynchronize(h->stream_red);
-    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : h->sync_ev) (void)hipEventDestroy(e);
-    if (h->stream_red) (void)hipStreamDestroy(h->stream_red);
-    if (h->tv_ev) (void)hipEventDestroy(h->tv_ev);
-    hz_fbi::fb_resp_free(h);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+    (void)h->stream.sync();
+    if (h->stream_red) (void)h->stream_red.sync();   // (made at the first chunked LTI call)
+    hz_fbi::fb_resp_free(h);   // (its side stream's work done, the trace written)
     delete h;
     return HZ_OK;
 }
@@ -1257,21 +1236,12 @@ int hz_fb_process(hz_fb* h, const double* in, double* out, size_t n) {
 
 int hz_fb_set_stream(hz_fb* h, void* s) {
     HZ_TRY(fb_check(h));
-    HZ_TRY_HIP(hipStreamSynchronize(h->stream));
-    if (h->own_stream) HZ_TRY_HIP(hipStreamDestroy(h->stream));
-    if (s) {
-        h->stream = (hipStream_t)s;
-        h->own_stream = false;
-    } else {
-        HZ_TRY_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        h->own_stream = true;
-    }
-    return HZ_OK;
+    return h->stream.rebind(s, hz::NullMeans::Private);
 }
 
 int hz_fb_get_stream(hz_fb* h, void** s) {
     if (!h || !s) return HZ_E_INVALID;
-    *s = (void*)h->stream;
+    *s = (void*)(hipStream_t)h->stream;
     return HZ_OK;
 }
 
@@ -1392,7 +1362,7 @@ int hz_fb_profile(hz_fb* h, int enable) {
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     h->prof = enable != 0;
     h->prof_rep = enable > 1 ? std::min(enable, 64) : 1;
-    h->ev_used = 0;
+    h->ev.rewind();
     h->prof_launches = 0;
     return HZ_OK;
 }
@@ -1402,7 +1372,7 @@ int hz_fb_profile_read(hz_fb* h, double* segment_ms, double* mix_ms, double* red
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     if (h->stream_red) HZ_TRY_HIP(hipStreamSynchronize(h->stream_red));
     double sg = 0, m = 0, r = 0;
-    for (size_t i = 0; i + 5 <= h->ev_used; i += 5) {
+    for (size_t i = 0; i + 5 <= h->ev.used(); i += 5) {   // complete quintuplets; no rewind: a read keeps the counters
         float a = 0, b = 0, c = 0;
         const unsigned char skip = h->ev_skip[i / 5];
         const hipEvent_t e1 = (skip & 2) ? h->ev[i] : h->ev[i + 1];

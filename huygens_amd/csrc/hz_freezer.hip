@@ -231,6 +231,7 @@ int ilog2(int N) {
 }  // namespace
 
 struct hz_frz {
+    hz::Stream stream;
     int N = 0, laps = 0, stride = 0, M = 0, size = 0, lg = 0, device = 0;
     long T = 0;
     bool frozen = false;
@@ -252,23 +253,15 @@ struct hz_frz {
     std::vector<SlotSrc> v_maps;
     hz::PinBuf<char> h_tab;
     hz::DevBuf<double> d_in, d_out;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
     bool prof = false;                 // HIP events around each frz_out_kernel launch
-    std::vector<hipEvent_t> ev;
-    size_t ev_used = 0;
+    hz::ProfEvents ev;
     long launches = 0;
 };
 
 namespace {
 
 int frz_check(hz_frz* h) {
-    if (!h) {
-        hz::set_error("null hz_frz handle");
-        return HZ_E_INVALID;
-    }
-    HZ_TRY_HIP(hipSetDevice(h->device));
-    return HZ_OK;
+    return hz::check_handle(h, "hz_frz");
 }
 
 // One chunk [T0, T0 + n) with its events (at relative to T0, ascending).
@@ -467,14 +460,7 @@ int frz_chunk(hz_frz* h, const double* d_in, double* d_out, long n, const hz_frz
     if (n > 0) {
         hipEvent_t* e = nullptr;
         if (h->prof) {
-            if (h->ev_used + 2 > h->ev.size())
-                for (int q = 0; q < 64; ++q) {
-                    hipEvent_t ne;
-                    HZ_TRY_HIP(hz::prof_event_create(&ne));
-                    h->ev.push_back(ne);
-                }
-            e = &h->ev[h->ev_used];
-            h->ev_used += 2;
+            HZ_TRY(h->ev.take(2, &e));
             HZ_TRY_HIP(hipEventRecord(e[0], h->stream));
         }
         hipLaunchKernelGGL(frz_out_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0,
@@ -547,7 +533,7 @@ int hz_frz_create(int N, int laps, double width, int device, hz_frz** out) {
         tw[k] = make_double2((double)cosl(ang), (double)sinl(ang));
     }
     const size_t MN = (size_t)h->M * N;
-    bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess;
+    bool ok = h->stream.create() == HZ_OK;
     ok = ok && h->d_ring.reserve(H) == HZ_OK && h->d_win.reserve(N) == HZ_OK && h->d_tw.reserve(N / 2) == HZ_OK;
     ok = ok && h->d_norm.reserve(MN) == HZ_OK && h->d_phase.reserve(MN) == HZ_OK;
     ok = ok && h->d_ifstate.reserve(MN) == HZ_OK && h->d_ifopen.reserve(MN) == HZ_OK;
@@ -572,11 +558,9 @@ int hz_frz_create(int N, int laps, double width, int device, hz_frz** out) {
     }
     if (!ok) {
         hz::set_error("hz_frz_create: device allocation failed");
-        if (h->stream) (void)hipStreamDestroy(h->stream);
         delete h;
         return HZ_E_ALLOC;
     }
-    h->own_stream = true;
     *out = h;
     return HZ_OK;
 }
@@ -584,9 +568,7 @@ int hz_frz_create(int N, int laps, double width, int device, hz_frz** out) {
 int hz_frz_destroy(hz_frz* h) {
     if (!h) return HZ_OK;
     (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+    (void)h->stream.sync();
     delete h;
     return HZ_OK;
 }
@@ -595,7 +577,7 @@ int hz_frz_profile(hz_frz* h, int enable) {
     HZ_TRY(frz_check(h));
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     h->prof = enable != 0;
-    h->ev_used = 0;
+    h->ev.rewind();
     h->launches = 0;
     return HZ_OK;
 }
@@ -604,11 +586,7 @@ int hz_frz_profile_read(hz_frz* h, double* ms, long* launches) {
     HZ_TRY(frz_check(h));
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     double m = 0;
-    for (size_t i = 0; i + 2 <= h->ev_used; i += 2) {
-        float x = 0;
-        HZ_TRY_HIP(hipEventElapsedTime(&x, h->ev[i], h->ev[i + 1]));
-        m += x;
-    }
+    HZ_TRY(h->ev.elapsed(2, 0, 1, &m));
     if (ms) *ms = m;
     if (launches) *launches = h->launches;
     return HZ_OK;
@@ -674,11 +652,7 @@ int hz_frz_unfreeze(hz_frz* h) {
 
 int hz_frz_set_stream(hz_frz* h, void* stream) {
     HZ_TRY(frz_check(h));
-    HZ_TRY_HIP(hipStreamSynchronize(h->stream));
-    if (h->own_stream) HZ_TRY_HIP(hipStreamDestroy(h->stream));
-    h->stream = (hipStream_t)stream;
-    h->own_stream = false;
-    return HZ_OK;
+    return h->stream.rebind(stream, hz::NullMeans::Legacy);
 }
 
 int hz_frz_synchronize(hz_frz* h) {

@@ -142,6 +142,7 @@ __global__ __launch_bounds__(kThreads) void gran_kernel(GranArgs a) {
 }  // namespace
 
 struct hz_gran {
+    hz::Stream stream;
     long uid = 0;                     // unique per handle (the per-sample server's grain-cache key)
     unsigned polyphony = 0, size = 0;
     int device = 0;
@@ -154,14 +155,11 @@ struct hz_gran {
     hz::DevBuf<double> d_ring;
     hz::DevBuf<char> d_g;             // the call's grains (GrainDev) + tile lists (bytes)
     hz::PinBuf<char> h_g;             // pinned staging of the same
-    hipEvent_t up_ev = nullptr;
+    hz::Event up_ev;
     bool up_pending = false;
     hz::DevBuf<double> d_in, d_out;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
     bool prof = false;
-    std::vector<hipEvent_t> ev;
-    size_t ev_used = 0;
+    hz::ProfEvents ev;
     long launches = 0, grain_samples = 0;
     bool pending = false;             // block work queued on the stream since the last synchronisation
     // per-sample calls (hz_gran_sample): the grains that may still read, in voice order, in pinned
@@ -175,12 +173,7 @@ struct hz_gran {
 namespace {
 
 int gran_check(hz_gran* h) {
-    if (!h) {
-        hz::set_error("null hz_gran handle");
-        return HZ_E_INVALID;
-    }
-    HZ_TRY_HIP(hipSetDevice(h->device));
-    return HZ_OK;
+    return hz::check_handle(h, "hz_gran");
 }
 
 // granulator.h:51-79 made at the position "after the read of sample t"; ticks0 = 1 when
@@ -304,14 +297,7 @@ int gran_run(hz_gran* h, const double* d_in, double* d_out, long n, const hz_gra
         a.wrap1 = 0xffffffffu % h->size;
         hipEvent_t* e = nullptr;
         if (h->prof) {
-            if (h->ev_used + 2 > h->ev.size())
-                for (int q = 0; q < 64; ++q) {
-                    hipEvent_t ne;
-                    HZ_TRY_HIP(hz::prof_event_create(&ne));
-                    h->ev.push_back(ne);
-                }
-            e = &h->ev[h->ev_used];
-            h->ev_used += 2;
+            HZ_TRY(h->ev.take(2, &e));
             HZ_TRY_HIP(hipEventRecord(e[0], h->stream));
         }
         hipLaunchKernelGGL(gran_kernel, dim3((unsigned)((m + kThreads - 1) / kThreads)), dim3(kThreads), 0,
@@ -357,18 +343,15 @@ int hz_gran_create(unsigned polyphony, unsigned buffer_size, int device, hz_gran
     long C = 1;
     while (C < (long)h->size + kChunk) C <<= 1;
     h->mask = C - 1;
-    bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&h->up_ev, hipEventDisableTiming) == hipSuccess;
+    bool ok = h->stream.create() == HZ_OK;
+    ok = ok && h->up_ev.create(hipEventDisableTiming) == HZ_OK;
     ok = ok && h->d_ring.reserve(C) == HZ_OK;
     ok = ok && hipMemset(h->d_ring, 0, sizeof(double) * C) == hipSuccess;   // Buffer: zeroed
     if (!ok) {
         hz::set_error("hz_gran_create: device allocation failed");
-        if (h->up_ev) (void)hipEventDestroy(h->up_ev);
-        if (h->stream) (void)hipStreamDestroy(h->stream);
         delete h;
         return HZ_E_ALLOC;
     }
-    h->own_stream = true;
     *out = h;
     return HZ_OK;
 }
@@ -376,10 +359,7 @@ int hz_gran_create(unsigned polyphony, unsigned buffer_size, int device, hz_gran
 int hz_gran_destroy(hz_gran* h) {
     if (!h) return HZ_OK;
     (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    if (h->up_ev) (void)hipEventDestroy(h->up_ev);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+    (void)h->stream.sync();
     delete h;
     return HZ_OK;
 }
@@ -475,11 +455,7 @@ int hz_gran_activity(hz_gran* h, unsigned* activity) {
 
 int hz_gran_set_stream(hz_gran* h, void* stream) {
     HZ_TRY(gran_check(h));
-    HZ_TRY_HIP(hipStreamSynchronize(h->stream));
-    if (h->own_stream) HZ_TRY_HIP(hipStreamDestroy(h->stream));
-    h->stream = (hipStream_t)stream;
-    h->own_stream = false;
-    return HZ_OK;
+    return h->stream.rebind(stream, hz::NullMeans::Legacy);
 }
 
 int hz_gran_synchronize(hz_gran* h) {
@@ -492,7 +468,7 @@ int hz_gran_profile(hz_gran* h, int enable) {
     HZ_TRY(gran_check(h));
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     h->prof = enable != 0;
-    h->ev_used = 0;
+    h->ev.rewind();
     h->launches = 0;
     h->grain_samples = 0;
     return HZ_OK;
@@ -502,15 +478,11 @@ int hz_gran_profile_read(hz_gran* h, double* ms, long* launches, long* grain_sam
     HZ_TRY(gran_check(h));
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     double tot = 0.0;
-    for (size_t i = 0; i + 1 < h->ev_used; i += 2) {
-        float t = 0.f;
-        HZ_TRY_HIP(hipEventElapsedTime(&t, h->ev[i], h->ev[i + 1]));
-        tot += t;
-    }
+    HZ_TRY(h->ev.elapsed(2, 0, 1, &tot));
     if (ms) *ms = tot;
     if (launches) *launches = h->launches;
     if (grain_samples) *grain_samples = h->grain_samples;
-    h->ev_used = 0;
+    h->ev.rewind();
     h->launches = 0;
     h->grain_samples = 0;
     return HZ_OK;

@@ -314,6 +314,7 @@ __global__ __launch_bounds__(kMixSamples* kMixSlices) void het_mix_kernel(const 
 }  // namespace
 
 struct hz_het {
+    hz::Stream stream;
     int N = 0, order = 1, sorder = 1, device = 0;
     long Np = 0, G = 0;
     unsigned width = 0, W1 = 1, r = 0;   // RMSbank origin (decrements per sample)
@@ -329,23 +330,15 @@ struct hz_het {
     hz::DevBuf<double> d_part;
     long chunk = 0;                       // samples per launch pair
     hz::DevBuf<double> d_in, d_out;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
     bool prof = false;
-    std::vector<hipEvent_t> ev;
-    size_t ev_used = 0;
+    hz::ProfEvents ev;
     long launches = 0, channel_samples = 0;
 };
 
 namespace {
 
 int het_check(hz_het* h) {
-    if (!h) {
-        hz::set_error("null hz_het handle");
-        return HZ_E_INVALID;
-    }
-    HZ_TRY_HIP(hipSetDevice(h->device));
-    return HZ_OK;
+    return hz::check_handle(h, "hz_het");
 }
 
 // stickbank.h:197-217: coefficients of the monic polynomial with `order` roots at rad
@@ -434,14 +427,7 @@ int het_run(hz_het* h, const double* d_in, double* d_out, long n) {
         for (int k = 0; k < kMaxStick; ++k) a.back[k] = h->back[k];
         hipEvent_t* e = nullptr;
         if (h->prof) {
-            if (h->ev_used + 2 > h->ev.size())
-                for (int q = 0; q < 64; ++q) {
-                    hipEvent_t ne;
-                    HZ_TRY_HIP(hz::prof_event_create(&ne));
-                    h->ev.push_back(ne);
-                }
-            e = &h->ev[h->ev_used];
-            h->ev_used += 2;
+            HZ_TRY(h->ev.take(2, &e));
             HZ_TRY_HIP(hipEventRecord(e[0], h->stream));
         }
         hipLaunchKernelGGL(chain_kernel(h->order, h->sorder, h->width > (unsigned)kDist), dim3((unsigned)h->G),
@@ -499,7 +485,7 @@ int hz_het_create(int channels, int order, const double* radii, double thresh, d
     if (const char* e = std::getenv("HZ_HET_CHUNK"))   // test hook: force launch splits
         h->chunk = std::max(1L, std::min(h->chunk, std::atol(e)));
     const size_t ring_bytes = sizeof(double) * (size_t)h->W1 * h->Np;
-    bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess;
+    bool ok = h->stream.create() == HZ_OK;
     ok = ok && h->d_st.reserve((size_t)F_COUNT * h->Np) == HZ_OK;
     ok = ok && h->d_ring.reserve((size_t)h->W1 * h->Np) == HZ_OK;
     ok = ok && h->d_act.reserve(2 * (size_t)h->Np) == HZ_OK;
@@ -514,7 +500,6 @@ int hz_het_create(int channels, int order, const double* radii, double thresh, d
         hz_het_destroy(h);
         return HZ_E_ALLOC;
     }
-    h->own_stream = true;
     {   // phases and frequencies start at 1 (oscbank.h:44-45)
         std::vector<double> ones(h->Np, 1.0);
         int rc = HZ_OK;
@@ -533,9 +518,7 @@ int hz_het_create(int channels, int order, const double* radii, double thresh, d
 int hz_het_destroy(hz_het* h) {
     if (!h) return HZ_OK;
     (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+    (void)h->stream.sync();
     delete h;
     return HZ_OK;
 }
@@ -653,11 +636,7 @@ int hz_het_state(hz_het* h, int what, double* dst) {
 
 int hz_het_set_stream(hz_het* h, void* stream) {
     HZ_TRY(het_check(h));
-    HZ_TRY_HIP(hipStreamSynchronize(h->stream));
-    if (h->own_stream) HZ_TRY_HIP(hipStreamDestroy(h->stream));
-    h->stream = (hipStream_t)stream;
-    h->own_stream = false;
-    return HZ_OK;
+    return h->stream.rebind(stream, hz::NullMeans::Legacy);
 }
 
 int hz_het_synchronize(hz_het* h) {
@@ -670,7 +649,7 @@ int hz_het_profile(hz_het* h, int enable) {
     HZ_TRY(het_check(h));
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     h->prof = enable != 0;
-    h->ev_used = 0;
+    h->ev.rewind();
     h->launches = 0;
     h->channel_samples = 0;
     return HZ_OK;
@@ -680,15 +659,11 @@ int hz_het_profile_read(hz_het* h, double* ms, long* launches, long* channel_sam
     HZ_TRY(het_check(h));
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     double tot = 0.0;
-    for (size_t i = 0; i + 1 < h->ev_used; i += 2) {
-        float t = 0.f;
-        HZ_TRY_HIP(hipEventElapsedTime(&t, h->ev[i], h->ev[i + 1]));
-        tot += t;
-    }
+    HZ_TRY(h->ev.elapsed(2, 0, 1, &tot));
     if (ms) *ms = tot;
     if (launches) *launches = h->launches;
     if (channel_samples) *channel_samples = h->channel_samples;
-    h->ev_used = 0;
+    h->ev.rewind();
     h->launches = 0;
     h->channel_samples = 0;
     return HZ_OK;

@@ -252,6 +252,7 @@ void build_orec(double wr, double wi, double* rec) {
 }  // namespace
 
 struct hz_osc {
+    hz::Stream stream;
     int N = 0, N_total = 0, begin = 0, device = 0;
     std::vector<double> wr, wi;               // staged frequencies (local)
     std::vector<unsigned char> active;        // local active flags
@@ -262,11 +263,8 @@ struct hz_osc {
     hz::DevBuf<int> d_act;
     hz::DevBuf<unsigned char> d_active;
     int target_groups = 256;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
     bool prof = false;
-    std::vector<hipEvent_t> ev;
-    size_t ev_used = 0;
+    hz::ProfEvents ev;
     long launches = 0;
     // per-sample calls (operator() / mixdown() / tick() of the drop-in) are served from a
     // speculative block: the phasors and mixes of the next la_L samples rendered at once from a
@@ -281,12 +279,7 @@ struct hz_osc {
 namespace {
 
 int osc_check(hz_osc* h) {
-    if (!h) {
-        hz::set_error("null hz_osc handle");
-        return HZ_E_INVALID;
-    }
-    HZ_TRY_HIP(hipSetDevice(h->device));
-    return HZ_OK;
+    return hz::check_handle(h, "hz_osc");
 }
 
 int osc_local(const hz_osc* h, int i) {
@@ -321,14 +314,7 @@ int osc_launch(hz_osc* h, double* d_mix, double* d_per_band, long n) {
     const int A = (int)h->act.size();
     hipEvent_t* e = nullptr;
     if (h->prof) {
-        if (h->ev_used + 2 > h->ev.size())
-            for (int q = 0; q < 128; ++q) {
-                hipEvent_t ne;
-                HZ_TRY_HIP(hz::prof_event_create(&ne));
-                h->ev.push_back(ne);
-            }
-        e = &h->ev[h->ev_used];
-        h->ev_used += 2;
+        HZ_TRY(h->ev.take(2, &e));
         HZ_TRY_HIP(hipEventRecord(e[0], h->stream));
     }
     if (d_per_band) {
@@ -445,8 +431,7 @@ int hz_osc_create_shard(int N_total, int begin, int count, double k, int device,
         hz_osc_destroy(h);
         return code;
     };
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail(HZ_E_HIP);
-    h->own_stream = true;
+    if (h->stream.create() != HZ_OK) return fail(HZ_E_HIP);
     if (h->d_rec.reserve((size_t)count * ORec::SIZE) || h->d_z.reserve((size_t)2 * count) ||
         h->d_act.reserve(count) || h->d_active.reserve(count)) {
         hz::set_error("hipMalloc failed for oscbank state");
@@ -465,9 +450,7 @@ int hz_osc_create(int N, double k, int device, hz_osc** out) { return hz_osc_cre
 int hz_osc_destroy(hz_osc* h) {
     if (!h) return HZ_OK;
     (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+    (void)h->stream.sync();
     delete h;
     return HZ_OK;
 }
@@ -620,16 +603,7 @@ int hz_osc_set_phases(hz_osc* h, const double* z) {
 
 int hz_osc_set_stream(hz_osc* h, void* s) {
     HZ_TRY(osc_check(h));
-    HZ_TRY_HIP(hipStreamSynchronize(h->stream));
-    if (h->own_stream) HZ_TRY_HIP(hipStreamDestroy(h->stream));
-    if (s) {
-        h->stream = (hipStream_t)s;
-        h->own_stream = false;
-    } else {
-        HZ_TRY_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        h->own_stream = true;
-    }
-    return HZ_OK;
+    return h->stream.rebind(s, hz::NullMeans::Private);
 }
 
 int hz_osc_synchronize(hz_osc* h) {
@@ -648,7 +622,7 @@ int hz_osc_profile(hz_osc* h, int enable) {
     HZ_TRY(osc_check(h));
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     h->prof = enable != 0;
-    h->ev_used = 0;
+    h->ev.rewind();
     h->launches = 0;
     return HZ_OK;
 }
@@ -657,11 +631,7 @@ int hz_osc_profile_read(hz_osc* h, double* ms, long* launches) {
     HZ_TRY(osc_check(h));
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     double m = 0;
-    for (size_t i = 0; i + 2 <= h->ev_used; i += 2) {
-        float x = 0;
-        HZ_TRY_HIP(hipEventElapsedTime(&x, h->ev[i], h->ev[i + 1]));
-        m += x;
-    }
+    HZ_TRY(h->ev.elapsed(2, 0, 1, &m));   // (no rewind: a read keeps the counters)
     if (ms) *ms = m;
     if (launches) *launches = h->launches;
     return HZ_OK;

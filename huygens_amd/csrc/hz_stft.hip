@@ -1158,6 +1158,7 @@ std::vector<double2> twiddles(int N) {
 }  // namespace
 
 struct hz_stft {
+    hz::Stream stream;
     int N = 0, laps = 0, stride = 0, lg = 0, window = 0, proc = 0, device = 0, R = 0;
     double p0 = 0, p1 = 0;
     hz_stft_proc host_proc = nullptr;
@@ -1174,14 +1175,11 @@ struct hz_stft {
     int hcur = 0;
     hz::DevBuf<double> d_in, d_out;            // host-buffer calls: [Re | Im]
     std::vector<double2> h_spec, h_out;   // host-processor path: spectra + per-slot out buffers
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
     bool prof = false;
     long chunk = 0;        // samples per internal block (a frame launch covers one)
     int prof_repeat = 1;   // frame launches per block while profiling (hz_stft_profile)
     bool pair_ok = true;   // two real frames per transform (stft_pair_kernel)
-    std::vector<hipEvent_t> ev;
-    size_t ev_used = 0;
+    hz::ProfEvents ev;
     long launches = 0;
     // time-range shards: frame f is computed here iff (f / sh_block) % sh_world == sh_rank
     long sh_block = 1;
@@ -1204,12 +1202,7 @@ struct hz_stft {
 namespace {
 
 int stft_check(hz_stft* h) {
-    if (!h) {
-        hz::set_error("null hz_stft handle");
-        return HZ_E_INVALID;
-    }
-    HZ_TRY_HIP(hipSetDevice(h->device));
-    return HZ_OK;
+    return hz::check_handle(h, "hz_stft");
 }
 
 // number of frames with completion time e_f = s_f + N - 1 < T
@@ -1357,14 +1350,7 @@ int stft_block(hz_stft* h, const double* d_re, const double* d_im, double* d_ore
 
     hipEvent_t* e = nullptr;
     if (h->prof) {
-        if (h->ev_used + 3 > h->ev.size())
-            for (int q = 0; q < 96; ++q) {
-                hipEvent_t ne;
-                HZ_TRY_HIP(hz::prof_event_create(&ne));
-                h->ev.push_back(ne);
-            }
-        e = &h->ev[h->ev_used];
-        h->ev_used += 3;
+        HZ_TRY(h->ev.take(3, &e));
         HZ_TRY_HIP(hipEventRecord(e[0], h->stream));
     }
     const long f_first = frames_before(h, h->T), f_done = frames_before(h, h->T + n);
@@ -1561,7 +1547,7 @@ int stft_create(const char* who, int max_n, int N, int laps, int window, int pro
     }
     h->h_win = win;
     const std::vector<double2> tw = twiddles(N);
-    bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess;
+    bool ok = h->stream.create() == HZ_OK;
     ok = ok && h->d_win.reserve(N) == HZ_OK;
     // N = 4096: the specialised pair kernel's pass tables after the N/2 table (p4::kTwLen)
     std::vector<double2> twx = tw;
@@ -1598,11 +1584,9 @@ int stft_create(const char* who, int max_n, int N, int laps, int window, int pro
     }
     if (!ok) {
         hz::set_error("%s: device allocation failed", who);
-        if (h->stream) (void)hipStreamDestroy(h->stream);
         delete h;
         return HZ_E_ALLOC;
     }
-    h->own_stream = true;
     static bool attr = false;
     if (!attr) {   // padded frame: 2 (N + N/16) doubles of LDS per workgroup (136 KB at N = 8192)
         const int lds = (int)std::max(frame_lds(kMaxN), sizeof(double) * (2 * kMaxN + 2 * (kThreads / 64)));
@@ -1638,9 +1622,7 @@ int hz_stft_create_long(int N, int laps, int window, int proc, double p0, double
 int hz_stft_destroy(hz_stft* h) {
     if (!h) return HZ_OK;
     (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+    (void)h->stream.sync();
     delete h;
     return HZ_OK;
 }
@@ -1915,11 +1897,7 @@ int hz_stft_frames(hz_stft* h, long* frames, long* samples) {
 
 int hz_stft_set_stream(hz_stft* h, void* stream) {
     HZ_TRY(stft_check(h));
-    HZ_TRY_HIP(hipStreamSynchronize(h->stream));
-    if (h->own_stream) HZ_TRY_HIP(hipStreamDestroy(h->stream));
-    h->stream = (hipStream_t)stream;
-    h->own_stream = false;
-    return HZ_OK;
+    return h->stream.rebind(stream, hz::NullMeans::Legacy);
 }
 
 int hz_stft_synchronize(hz_stft* h) {
@@ -1933,7 +1911,7 @@ int hz_stft_profile(hz_stft* h, int enable) {
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     h->prof = enable != 0;
     h->prof_repeat = enable > 1 ? enable : 1;
-    h->ev_used = 0;
+    h->ev.rewind();
     h->launches = 0;
     return HZ_OK;
 }
@@ -1942,17 +1920,12 @@ int hz_stft_profile_read(hz_stft* h, double* frame_ms, double* ola_ms, long* blo
     HZ_TRY(stft_check(h));
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     double fm = 0.0, om = 0.0;
-    for (size_t i = 0; i + 2 < h->ev_used; i += 3) {
-        float t0 = 0.f, t1 = 0.f;
-        HZ_TRY_HIP(hipEventElapsedTime(&t0, h->ev[i], h->ev[i + 1]));
-        HZ_TRY_HIP(hipEventElapsedTime(&t1, h->ev[i + 1], h->ev[i + 2]));
-        fm += t0;
-        om += t1;
-    }
+    HZ_TRY(h->ev.elapsed(3, 0, 1, &fm));
+    HZ_TRY(h->ev.elapsed(3, 1, 2, &om));
     if (frame_ms) *frame_ms = fm / (h->proc != HZ_PROC_HOST ? h->prof_repeat : 1);   // per single launch
     if (ola_ms) *ola_ms = om;
     if (blocks) *blocks = h->launches;
-    h->ev_used = 0;
+    h->ev.rewind();
     h->launches = 0;
     return HZ_OK;
 }
@@ -1963,11 +1936,11 @@ int hz_stft_profile_read(hz_stft* h, double* frame_ms, double* ola_ms, long* blo
 // Cosine
 // ---------------------------------------------------------------------------
 struct hz_dct {
+    hz::Stream stream;
     int N = 0, lg = 0, device = 0;
     hz::PinBuf<double> h_in, h_out;   // pinned, owned (fourier.h:201-207)
     hz::DevBuf<double> d_a, d_b;
     hz::DevBuf<double2> d_tw, d_rot;
-    hipStream_t stream = nullptr;
     // N > kMaxN: the two passes of hz_fft_long.h through a workspace [batch][N]
     int lg1 = 0, lg2 = 0;
     hz::DevBuf<double2> d_tw1, d_tw2, d_ws;
@@ -2035,7 +2008,7 @@ int hz_dct_create(int N, int device, hz_dct** out) {
         const long double a = -pi * k / (2.0L * N);
         rot[k] = make_double2((double)cosl(a), (double)sinl(a));
     }
-    bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess;
+    bool ok = h->stream.create() == HZ_OK;
     ok = ok && h->h_in.reserve(N) == HZ_OK && h->h_out.reserve(N) == HZ_OK;
     ok = ok && h->d_a.reserve(N) == HZ_OK && h->d_b.reserve(N) == HZ_OK;
     ok = ok && h->d_tw.reserve(N / 2) == HZ_OK && h->d_rot.reserve(N) == HZ_OK;
@@ -2052,7 +2025,6 @@ int hz_dct_create(int N, int device, hz_dct** out) {
     }
     if (!ok) {
         hz::set_error("hz_dct_create: allocation failed");
-        if (h->stream) (void)hipStreamDestroy(h->stream);
         delete h;
         return HZ_E_ALLOC;
     }
@@ -2065,8 +2037,7 @@ int hz_dct_create(int N, int device, hz_dct** out) {
 int hz_dct_destroy(hz_dct* h) {
     if (!h) return HZ_OK;
     (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    (void)h->stream.sync();
     delete h;
     return HZ_OK;
 }

@@ -236,6 +236,7 @@ __global__ __launch_bounds__(256) void sub_reduce_kernel(const double* __restric
 // Subtractive<double, N>
 // ---------------------------------------------------------------------------
 struct hz_sub : hz::MinNotes {
+    hz::Stream stream;
     int N = 1, device = 0;
     double decay = 0, resonance = 0, norm = 1, attack = 0;
     std::vector<double> amp;   // amplitudes[v]
@@ -250,22 +251,14 @@ struct hz_sub : hz::MinNotes {
     hz::DevBuf<double> d_x, d_v, d_eq, d_guide, d_act, d_rows, d_amp, d_dec, d_state, d_part, d_in, d_out;
     hz::DevBuf<Coef> d_coef, d_cur;
     std::vector<double> amp_rows;   // [n + 1][V] envelope rows of the piece being rendered
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
     bool prof = false;
-    std::vector<hipEvent_t> ev;     // profile: 5 per piece (start, physics, coefficients, resonators, reduce)
-    size_t ev_used = 0;
+    hz::ProfEvents ev;     // profile: 5 per piece (start, physics, coefficients, resonators, reduce)
 };
 
 namespace {
 
 int sub_check(hz_sub* h) {
-    if (!h) {
-        hz::set_error("null hz_sub handle");
-        return HZ_E_INVALID;
-    }
-    HZ_TRY_HIP(hipSetDevice(h->device));
-    return HZ_OK;
+    return hz::check_handle(h, "hz_sub");
 }
 
 int sub_law_check(int law) {
@@ -397,14 +390,7 @@ int sub_render(hz_sub* h, const double* d_in, double* d_dst, long n) {
         HZ_TRY(sub_upload_call(h, m + 1));
         hipEvent_t* e = nullptr;
         if (h->prof) {
-            if (h->ev_used + 5 > h->ev.size())
-                for (int q = 0; q < 160; ++q) {
-                    hipEvent_t ne;
-                    HZ_TRY_HIP(hz::prof_event_create(&ne));
-                    h->ev.push_back(ne);
-                }
-            e = &h->ev[h->ev_used];
-            h->ev_used += 5;
+            HZ_TRY(h->ev.take(5, &e));
             HZ_TRY_HIP(hipEventRecord(e[0], h->stream));
         }
         HZ_TRY(sub_steps(h, steps));
@@ -453,8 +439,7 @@ int hz_sub_create(int voices, int overtones, int channels, double decay, double 
     std::vector<double> dec(overtones);
     for (int j = 0; j < overtones; ++j) dec[j] = std::pow(decay, j);
     auto init = [&]() -> int {
-        HZ_TRY_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        h->own_stream = true;
+        HZ_TRY(h->stream.create());
         HZ_TRY(h->d_x.reserve(P));
         HZ_TRY(h->d_v.reserve(P));
         HZ_TRY(h->d_eq.reserve(P));
@@ -486,9 +471,7 @@ int hz_sub_create(int voices, int overtones, int channels, double decay, double 
 int hz_sub_destroy(hz_sub* h) {
     if (!h) return HZ_OK;
     (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+    (void)h->stream.sync();
     delete h;
     return HZ_OK;
 }
@@ -613,16 +596,7 @@ int hz_sub_amplitudes(hz_sub* h, double* out) {
 
 int hz_sub_set_stream(hz_sub* h, void* s) {
     HZ_TRY(sub_check(h));
-    HZ_TRY_HIP(hipStreamSynchronize(h->stream));
-    if (h->own_stream) HZ_TRY_HIP(hipStreamDestroy(h->stream));
-    if (s) {
-        h->stream = (hipStream_t)s;
-        h->own_stream = false;
-    } else {
-        HZ_TRY_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        h->own_stream = true;
-    }
-    return HZ_OK;
+    return h->stream.rebind(s, hz::NullMeans::Private);
 }
 
 int hz_sub_tune_physics(hz_sub* h, int single_group_max, int tile) {
@@ -640,7 +614,7 @@ int hz_sub_profile(hz_sub* h, int enable) {
     HZ_TRY(sub_check(h));
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     h->prof = enable != 0;
-    h->ev_used = 0;
+    h->ev.rewind();
     return HZ_OK;
 }
 
@@ -648,12 +622,7 @@ int hz_sub_profile_read(hz_sub* h, double* physics_ms, double* coef_ms, double* 
     HZ_TRY(sub_check(h));
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     double ms[4] = {0, 0, 0, 0};
-    for (size_t i = 0; i + 5 <= h->ev_used; i += 5)
-        for (int q = 0; q < 4; ++q) {
-            float x = 0;
-            HZ_TRY_HIP(hipEventElapsedTime(&x, h->ev[i + q], h->ev[i + q + 1]));
-            ms[q] += x;
-        }
+    for (int q = 0; q < 4; ++q) HZ_TRY(h->ev.elapsed(5, q, q + 1, &ms[q]));   // (no rewind: a read keeps the counters)
     if (physics_ms) *physics_ms = ms[0];
     if (coef_ms) *coef_ms = ms[1];
     if (resonator_ms) *resonator_ms = ms[2];

@@ -118,6 +118,7 @@ int hz_fb_sample_many(hz_fb* const* handles, int count, const double* x, int dis
 int hz_fb_setter_seq(hz_fb* h, long long* seq);
 /* whether the handle is in per-sample mode, samples served, server workgroups taking part */
 int hz_fb_sample_info(hz_fb* h, int* active, long long* served, int* groups);
+/* hip_stream NULL: the handle goes back to a private non-blocking stream of its own */
 int hz_fb_set_stream(hz_fb* h, void* hip_stream);
 int hz_fb_get_stream(hz_fb* h, void** hip_stream);
 int hz_fb_synchronize(hz_fb* h);
@@ -135,6 +136,7 @@ int hz_fb_tune(hz_fb* h, int waves_per_group, int bands_per_wave);
  * enable > 1 (at most 64): the stationary engine's modal-path kernels run `enable`
  * times back to back between their events and the times read are per launch. */
 int hz_fb_profile(hz_fb* h, int enable);
+/* (reading does not reset the counters: only hz_fb_profile does) */
 int hz_fb_profile_read(hz_fb* h, double* segment_ms, double* mix_ms, double* reduce_ms, long* launches);
 /* workgroups wanted per launch before time segmentation kicks in (default: CU count) */
 int hz_fb_set_target_groups(hz_fb* h, int groups);
@@ -272,10 +274,12 @@ int hz_osc_phases(hz_osc* h, double* z);
 /* mixdown() of the current phasors (sum over the active set in index order) without a tick */
 int hz_osc_mixdown(hz_osc* h, double* mix);
 int hz_osc_set_phases(hz_osc* h, const double* z);
+/* hip_stream NULL: the handle goes back to a private non-blocking stream of its own */
 int hz_osc_set_stream(hz_osc* h, void* hip_stream);
 int hz_osc_synchronize(hz_osc* h);
 int hz_osc_set_target_groups(hz_osc* h, int groups);
 int hz_osc_profile(hz_osc* h, int enable);
+/* (reading does not reset the counters: only hz_osc_profile does) */
 int hz_osc_profile_read(hz_osc* h, double* ms, long* launches);
 
 /* ---- Additive<double>  (src/additive.h:11-71 + Minimizer note API,
@@ -304,9 +308,11 @@ int hz_add_fill(hz_add* h, double* out, size_t n);
 /* speculative blocks rendered, rollbacks (a setter inside a block), block length */
 int hz_add_lookahead_info(hz_add* h, long* blocks, long* rollbacks, long* block_len);
 int hz_add_fill_device(hz_add* h, double* d_out, size_t n);
+/* hip_stream NULL: the handle goes back to a private non-blocking stream of its own */
 int hz_add_set_stream(hz_add* h, void* hip_stream);
 int hz_add_set_target_groups(hz_add* h, int groups);
 int hz_add_profile(hz_add* h, int enable);
+/* (reading does not reset the counters: only hz_add_profile does) */
 int hz_add_profile_read(hz_add* h, double* ms, long* launches);
 
 /* Minimizer<T>::physics() (src/minimizer.h:61-108, src/particle.h) on the device: springs along each
@@ -340,6 +346,7 @@ int hz_add_positions(hz_add* h, double* out);
 int hz_add_tune_physics(hz_add* h, int single_group_max, int tile);
 /* with hz_add_profile on: milliseconds spent in the physics kernels and in the audio kernels of the
  * physics path since hz_add_profile(h, 1) */
+/* (reading does not reset the counters: only hz_add_profile does) */
 int hz_add_physics_profile_read(hz_add* h, double* physics_ms, double* audio_ms);
 
 /* ---- Subtractive<double, N>  (src/subtractive.h:15-101, the MIMO variant; note API and physics()
@@ -374,12 +381,14 @@ int hz_sub_peek(hz_sub* h, const double* in, double* out);
 /* particles[v * overtones + j]() (voices x overtones doubles) and amplitudes[v] (voices doubles) */
 int hz_sub_positions(hz_sub* h, double* out);
 int hz_sub_amplitudes(hz_sub* h, double* out);
+/* hip_stream NULL: the handle goes back to a private non-blocking stream of its own */
 int hz_sub_set_stream(hz_sub* h, void* hip_stream);
 /* as hz_add_tune_physics */
 int hz_sub_tune_physics(hz_sub* h, int single_group_max, int tile);
 /* with the profile on: milliseconds since hz_sub_profile(h, 1) in the physics kernels, the
  * coefficient kernel, the resonator kernel and the reduce kernel */
 int hz_sub_profile(hz_sub* h, int enable);
+/* (reading does not reset the counters: only hz_sub_profile does) */
 int hz_sub_profile_read(hz_sub* h, double* physics_ms, double* coef_ms, double* resonator_ms, double* reduce_ms);
 
 /* ---- Sinusoids<double>  (src/sinusoids.h:10-79), waveform cycle ------------ */
@@ -412,9 +421,11 @@ int hz_bowl_fill_device(hz_bowl* h, float* d_buffer, size_t bsize);
 int hz_bowl_render(hz_bowl* h, double* out, size_t n);
 int hz_bowl_render_device(hz_bowl* h, double* d_out, size_t n);
 int hz_bowl_phase(hz_bowl* h, double* phase);
+/* hip_stream NULL: the handle goes back to a private non-blocking stream of its own */
 int hz_bowl_set_stream(hz_bowl* h, void* hip_stream);
 int hz_bowl_set_target_groups(hz_bowl* h, int groups);
 int hz_bowl_profile(hz_bowl* h, int enable);
+/* (reading does not reset the counters: only hz_bowl_profile does) */
 int hz_bowl_profile_read(hz_bowl* h, double* ms, long* launches);
 
 /* ---- Delay<T> / Delaybank<T,N>  (src/delay.h:10-108 over src/buffer.h:9-86) ----
@@ -460,10 +471,12 @@ int hz_dly_tick(hz_dly* h, unsigned long count);
 int hz_dly_origin(hz_dly* h, unsigned* origin);            /* Buffer::origin after the last call */
 int hz_dly_info(hz_dly* h, long* chunk, unsigned* size);   /* sub-block length (-1: unbounded), ring size */
 int hz_dly_set_split(hz_dly* h, int mode);                 /* 0 auto, 1 workgroup per line, 2 launch per sub-block */
+/* hip_stream NULL: the null (legacy) stream itself is bound -- torch's default stream is handle 0 */
 int hz_dly_set_stream(hz_dly* h, void* hip_stream);
 int hz_dly_synchronize(hz_dly* h);
 int hz_dly_set_target_groups(hz_dly* h, int groups);
 int hz_dly_profile(hz_dly* h, int enable);
+/* (reading resets the counters) */
 int hz_dly_profile_read(hz_dly* h, double* ms, long* launches);
 
 /* ---- a Bowl block into a Delaybank (`bowl.fill(buf, n);
@@ -527,12 +540,14 @@ int hz_stft_process_slot(hz_stft* h, int slot);
 int hz_stft_set_frame_shard(hz_stft* h, int rank, int world, long block);
 /* frames completing within the first `samples` input samples of an (N, laps) engine */
 int hz_stft_frames_before(int N, int laps, long samples, long* frames);
+/* hip_stream NULL: the null (legacy) stream itself is bound -- torch's default stream is handle 0 */
 int hz_stft_set_stream(hz_stft* h, void* hip_stream);
 int hz_stft_synchronize(hz_stft* h);
 /* Event timing of the frame and overlap-add kernels.  enable > 1 repeats each block's
  * (idempotent) device-processor frame launch `enable` times between the events, so the
  * event overhead is amortised; profile_read then reports frame_ms per single launch. */
 int hz_stft_profile(hz_stft* h, int enable);
+/* (reading resets the counters) */
 int hz_stft_profile_read(hz_stft* h, double* frame_ms, double* ola_ms, long* blocks);
 
 /* ---- Cosine (src/fourier.h:197-234): Cosine(int N, double** in, double** out) ----
@@ -579,9 +594,11 @@ int hz_gran_process_device(hz_gran* h, const double* d_in, double* d_out, size_t
  * the device's per-sample server (no launch per sample); the same arithmetic as hz_gran_process */
 int hz_gran_sample(hz_gran* h, double x, double* y);
 int hz_gran_activity(hz_gran* h, unsigned* activity);   /* active voices; idle() 106-109 is == 0 */
+/* hip_stream NULL: the null (legacy) stream itself is bound -- torch's default stream is handle 0 */
 int hz_gran_set_stream(hz_gran* h, void* hip_stream);
 int hz_gran_synchronize(hz_gran* h);
 int hz_gran_profile(hz_gran* h, int enable);
+/* (reading resets the counters) */
 int hz_gran_profile_read(hz_gran* h, double* ms, long* launches, long* grain_samples);
 
 /* ---- Freezer<N> (src/fourier.h:389-562) with FFrame / IFrame / DFrame (236-387) ----
@@ -604,10 +621,12 @@ int hz_frz_unfreeze(hz_frz* h);                                                /
 int hz_frz_process(hz_frz* h, const double* in, double* out, size_t n, const hz_frz_event* ev, int nev);
 int hz_frz_process_device(hz_frz* h, const double* d_in, double* d_out, size_t n, const hz_frz_event* ev, int nev);
 int hz_frz_info(hz_frz* h, int* stride, int* frames, int* frozen);
+/* hip_stream NULL: the null (legacy) stream itself is bound -- torch's default stream is handle 0 */
 int hz_frz_set_stream(hz_frz* h, void* hip_stream);
 int hz_frz_synchronize(hz_frz* h);
 /* HIP-event timing of the output kernel (frz_out_kernel) launches while enabled */
 int hz_frz_profile(hz_frz* h, int enable);
+/* (reading does not reset the counters: only hz_frz_profile does) */
 int hz_frz_profile_read(hz_frz* h, double* ms, long* launches);
 
 /* ---- Filterbank with per-sample coefficient streams ----
@@ -661,9 +680,11 @@ int hz_het_open(hz_het* h, int bank, int on);                                   
 int hz_het_process(hz_het* h, const double* in, double* out, size_t n);
 int hz_het_process_device(hz_het* h, const double* d_in, double* d_out, size_t n);
 int hz_het_state(hz_het* h, int what, double* dst);
+/* hip_stream NULL: the null (legacy) stream itself is bound -- torch's default stream is handle 0 */
 int hz_het_set_stream(hz_het* h, void* hip_stream);
 int hz_het_synchronize(hz_het* h);
 int hz_het_profile(hz_het* h, int enable);
+/* (reading resets the counters) */
 int hz_het_profile_read(hz_het* h, double* ms, long* launches, long* channel_samples);
 
 #ifdef __cplusplus

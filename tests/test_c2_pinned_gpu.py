@@ -103,8 +103,10 @@ def test_c2_bench_sequence_per_block(gpu_lib, c2):
     from huygens_amd._lib import HZ_FB_PATH_RESPONSE
     g, o = c2
     rng = np.random.default_rng(1234)
+    from visibility import assert_band_states, band_peaks
     paths, worst = [], []
     stationary = 0
+    scale = None
     for call in range(8):
         x = rng.uniform(-1, 1, S).astype(np.float32).astype(np.float64)
         yg, yc = g.process(x), o.process(x)
@@ -116,6 +118,10 @@ def test_c2_bench_sequence_per_block(gpu_lib, c2):
         st_g, st_c = g.get_state(), o.state()
         sc = np.max(np.abs(st_c[2:2 + 2 * N]))
         assert np.max(np.abs(st_g[2:2 + 2 * N] - st_c[2:2 + 2 * N])) <= TIGHT * sc, call
+        # sc is the Nyquist band's state, ~1e8: every other band within 1e-8 of its own output peak
+        if scale is None:
+            scale = band_peaks(*resonant_coefficients(N, 0.999, 1.0), x[-16384:])
+        assert_band_states(st_g, st_c, N, scale, 1e-8, TIGHT)
         assert np.array_equal(st_g[:2], st_c[:2])                      # x history: exact
         # smoothers: the engine advances them in closed form (pin + s^n (p0 - pin)), the reference
         # one sample at a time -- the same value to a few ulps of the targets

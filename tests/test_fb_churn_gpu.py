@@ -14,6 +14,7 @@ import pytest
 from golden.spec_numpy import resonant_coefficients
 from oracle import OracleFilterbank
 from test_c2_pinned_gpu import block_errors
+from visibility import assert_band_states, band_peaks
 
 pytestmark = pytest.mark.gpu
 B = 1024
@@ -50,6 +51,7 @@ def test_mix_churn_streams(gpu_lib, N):
     rng = np.random.default_rng(N)
     _stationary(g, o, rng)
     worst, streamed = 0.0, 0
+    xs = []
     calls0 = g.stream_info()[2]
     for blk in range(150):
         if blk < 80 and blk % 5 == 2:   # 9 bands retuned every ~100 ms (tests/filterbank.cpp:217-252)
@@ -63,6 +65,7 @@ def test_mix_churn_streams(gpu_lib, N):
             g.mix(v)
             o.mix(v)
         x = rng.uniform(-1, 1, B)
+        xs.append(x)
         yg, yo = g.process(x), o.process(x)
         err, _ = block_errors(yg, yo)
         worst = max(worst, float(err.max()))
@@ -72,10 +75,14 @@ def test_mix_churn_streams(gpu_lib, N):
     assert streamed == 150 and g.stream_info()[2] - calls0 == 150
     # then a long call (the per-band / stationary engines take over from the streamed state)
     x = rng.uniform(-1, 1, 30000)
+    xs.append(x)
     err, _ = block_errors(g.process(x), o.process(x))
     assert err.max() <= 1e-7
     st_g, st_o = g.get_state(), o.get_state()
     assert np.max(np.abs(st_g - st_o)) <= 1e-8 * max(1.0, np.max(np.abs(st_o)))
+    # (that maximum is the Nyquist band's 1e8) every other band against its own output peak
+    fwd, back = resonant_coefficients(N, 0.999, 1.0)
+    assert_band_states(st_g, st_o, N, band_peaks(fwd, back, np.concatenate(xs)[-65536:]), 1e-8, 1e-8)
 
 
 def test_mix_churn_then_boost(gpu_lib):

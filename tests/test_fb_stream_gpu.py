@@ -13,6 +13,7 @@ import pytest
 from golden.spec_numpy import resonant_coefficients
 from oracle import OracleFilterbank
 from test_c2_pinned_gpu import NORTH_STAR, TIGHT, ThreadedOracle, block_errors
+from visibility import assert_band_states, band_peaks
 
 pytestmark = pytest.mark.gpu
 
@@ -44,9 +45,11 @@ def test_stream_small_bank_switches(gpu_lib):
     g, o = _bank(N, R=0.99, k_p=0.01, k_g=0.01)
     g.tune_response(0, 1)   # long calls of this small bank stationary too (cost model off)
     rng = np.random.default_rng(5)
+    inputs = []
 
     def run(n):
         x = rng.uniform(-1, 1, n).astype(np.float32).astype(np.float64)
+        inputs.append(x)
         yg, yc = g.process(x), o.process(x)
         _check(yg, yc)
         return g.last_path()
@@ -63,6 +66,9 @@ def test_stream_small_bank_switches(gpu_lib):
     st_g, st_c = g.get_state(), o.get_state()
     sc = np.max(np.abs(st_c[2:2 + 2 * N]))
     assert np.max(np.abs(st_g[2:2 + 2 * N] - st_c[2:2 + 2 * N])) <= TIGHT * sc
+    # (sc is the Nyquist band's 1e8: every other band against its own output peak too)
+    fwd, back = resonant_coefficients(N, 0.99, 1.0)
+    assert_band_states(st_g, st_c, N, band_peaks(fwd, back, np.concatenate(inputs)), 1e-8, TIGHT)
     assert np.array_equal(st_g[:2], st_c[:2])
     assert np.max(np.abs(st_g[2 + 2 * N:] - st_c[2 + 2 * N:])) <= 1e-12
     # streaming resumes after get_state without a gap
@@ -148,6 +154,7 @@ def test_stream_c2_exact_config_per_block(gpu_lib):
     for _ in range(2):
         x = rng.uniform(-1, 1, 480_000).astype(np.float32).astype(np.float64)
         _check(g.process(x), o.process(x))
+    scale = band_peaks(fwd, back, x[-16384:])   # each band's own output peak on this noise
     paths, worst = [], 0.0
 
     def block():
@@ -165,6 +172,7 @@ def test_stream_c2_exact_config_per_block(gpu_lib):
     st_g, st_c = g.get_state(), o.state()
     sc = np.max(np.abs(st_c[2:2 + 2 * N]))
     assert np.max(np.abs(st_g[2:2 + 2 * N] - st_c[2:2 + 2 * N])) <= TIGHT * sc
+    assert_band_states(st_g, st_c, N, scale, 1e-8, TIGHT)   # ... and band by band
     assert np.array_equal(st_g[:2], st_c[:2])
     # boost setter mid-stream (the reference's MIDI thread: tests/filterbank.cpp:236-244)
     g.boost(np.full(N, 0.75))
@@ -263,9 +271,11 @@ def test_stream_high_q_tail(gpu_lib):
     g, o = _bank(N, R=0.9999, k_p=0.01, k_g=0.01)
     g.tune_response(bands_per_sample=1)   # a 64-band bank: let the cost model pick the engines
     rng = np.random.default_rng(31)
+    xs = []
 
     def run(n, tol=1e-6):
         x = rng.uniform(-1, 1, n).astype(np.float32).astype(np.float64)
+        xs.append(x)
         yg, yc = g.process(x), o.process(x)
         err, _ = block_errors(yg, yc)
         assert err.max() <= tol, (n, g.last_path(), err.max())
@@ -281,6 +291,9 @@ def test_stream_high_q_tail(gpu_lib):
     st_g, st_c = g.get_state(), o.get_state()
     sc = np.max(np.abs(st_c[2:2 + 2 * N]))
     assert np.max(np.abs(st_g[2:2 + 2 * N] - st_c[2:2 + 2 * N])) <= 1e-6 * sc
+    # band by band (R = 0.9999: the states remember ~0.5 M inputs, the scale's window is all of them)
+    fwd, back = resonant_coefficients(N, 0.9999, 1.0)
+    assert_band_states(st_g, st_c, N, band_peaks(fwd, back, np.concatenate(xs)), 1e-8, 1e-6)
     assert [run(B) for _ in range(20)] == [HZ_FB_PATH_STREAM] * 20
     assert run(50_000) == HZ_FB_PATH_RESPONSE
     assert [run(B) for _ in range(40)] == [HZ_FB_PATH_STREAM] * 40

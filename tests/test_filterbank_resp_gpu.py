@@ -235,6 +235,9 @@ def test_c2_full_size_against_lti(gpu_lib):
         assert rel_err(yg, yt) < 1e-7, (i, rel_err(yg, yt))   # Nyquist double pole: TOL_STIFF
     assert g.last_path() == L.HZ_FB_PATH_RESPONSE
     assert states_close(g.get_state(), t.get_state(), 1e-7)
+    # (1e-7 of the Nyquist band's 1e8) band by band, each against its own output peak
+    from visibility import assert_band_states, band_peaks
+    assert_band_states(g.get_state(), t.get_state(), N, band_peaks(fwd, back, x[-16384:]), 1e-8, 1e-7)
 
 
 def test_time_range_shards(gpu_lib):
@@ -403,8 +406,10 @@ def test_time_range_shards_modal(gpu_lib, fill):
     for r, s in enumerate(shards):
         assert set_time_shards(s, r, 3, lambda h, full=full: full, lambda k, K_all=K_all: K_all if k > 1 else k)
         s.set_time_shard_fill(fill)
+    from visibility import band_peaks, band_state_errors
     rng = np.random.default_rng(12)
     modal_calls = 0
+    scale = None
     for n in [60000, 60000, 70001, 52000, 100003]:
         ready = all(s.stationary_ready(n) for s in shards)
         for s in shards:
@@ -436,5 +441,12 @@ def test_time_range_shards_modal(gpu_lib, fill):
         for (b0, cnt), s in zip(cuts, shards):
             gs = s.get_state()
             assert states_close(gs[O:O + cnt * O], st[O + b0 * O:O + (b0 + cnt) * O]), (n, b0)
+            # the last shard's scale above is the Nyquist band's 1e8: every regular band against
+            # its own output peak
+            if scale is None:
+                scale = band_peaks(fwd, back, x)
+            reg = min(b0 + cnt, N - 1) - b0
+            e = band_state_errors(gs[O:O + reg * O], st[O + b0 * O:O + (b0 + reg) * O], scale[b0:b0 + reg])
+            assert e.max() <= 1e-8, (n, b0, int(e.argmax()), e.max())
     assert modal_calls >= 2
     assert shards[2].modal_info()[2] == 1 and shards[0].modal_info()[2] == 0   # the Nyquist band: shard 2

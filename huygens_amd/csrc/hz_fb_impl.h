@@ -188,7 +188,7 @@ struct hz_fb {
         hz::DevBuf<double> d_H;          // [Qp][2048] complex partition spectra, then [Qp] bin 2048
         hz::DevBuf<double> d_Z;          // [rows][2048] complex window spectra, then [rows] bin 2048
         hz::DevBuf<double> d_Y;          // [B][2048] complex output spectra
-        hz::DevBuf<double> d_tw;         // W_4096^k, k < 2048 (complex)
+        hz::DevBuf<double> d_tw;         // W_4096^k in the transforms' thread order: forward, inverse (complex)
         // column-split path (hz_fb_col.h): W_4096^k for k < 4096, H in column layout, the inverse
         // columns T of a call, the combine's column map
         bool col_on = false;             // hz_fb_tune_response_engine (column split: opt-in)

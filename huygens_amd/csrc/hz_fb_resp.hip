@@ -181,9 +181,11 @@ __global__ __launch_bounds__(256) void resp_hsum_kernel(const double* __restrict
 // one thread per pair (k, kH - k), k = t + 256 i (k = 0 pairs with itself: X_0 and X_kH; thread
 // 0 also takes k = kH / 2).  Rows hold X_0 .. X_{kH-1} (X_0 real, imaginary part 0); X_kH (real)
 // is kept apart (nyq), so the MAC is one complex product per stored bin.
-// (POL: the row's store policy)
+// (POL: the row's store policy; twf: the forward twiddles in thread order, kTwFwd)
+constexpr int kTwRows = hz2k::kTwSlots + 4;   // a thread-order table: the stage twiddles, then W^(t + 256 i)
+constexpr int kTwFwd = 0, kTwInv = kTwRows * kThreads;   // the two tables in Resp::d_tw (double2)
 template <int POL, class Load>
-__device__ __forceinline__ void real_window_fwd(hz2k::Lds& s, Load load, const double2* __restrict__ tw,
+__device__ __forceinline__ void real_window_fwd(hz2k::Lds& s, Load load, const double2* __restrict__ twf,
                                                 double2* __restrict__ zrow, double* __restrict__ nyq,
                                                 bool stamps = false) {
     const int t = threadIdx.x;
@@ -198,10 +200,10 @@ __device__ __forceinline__ void real_window_fwd(hz2k::Lds& s, Load load, const d
         vi[i] = v.y;
     }
     hz2k::FwdTw ft;
-    ft.load(tw);
+    ft.load(twf);
     double2 w[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = tw[t + i * kThreads];
+    for (int i = 0; i < 4; ++i) w[i] = twf[(hz2k::kTwSlots + i) * kThreads + t];
 #ifdef HZ_DIAG_STAMPS
     if (stamps) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -233,7 +235,7 @@ __device__ __forceinline__ void real_window_fwd(hz2k::Lds& s, Load load, const d
 // Partition spectra H_p = FFT(h[pP, (p+1)P) zero-padded to F) / F (the inverse is unnormalised;
 // 1/F is a power of two)
 __global__ __launch_bounds__(kThreads) void resp_hspec_kernel(const double* __restrict__ h, long K,
-                                                             const double2* __restrict__ tw, double2* __restrict__ H,
+                                                             const double2* __restrict__ twf, double2* __restrict__ H,
                                                              double* __restrict__ Hn) {
     __shared__ hz2k::Lds s;
     const long p0 = (long)blockIdx.x * kP;
@@ -243,7 +245,7 @@ __global__ __launch_bounds__(kThreads) void resp_hspec_kernel(const double* __re
             auto g = [&](int k) { return (k < kP && p0 + k < K) ? h[p0 + k] * (1.0 / kF) : 0.0; };
             return make_double2(g(m), g(m + 1));
         },
-        tw,
+        twf,
         H + (long)blockIdx.x * kH, Hn + blockIdx.x);
 }
 
@@ -254,7 +256,7 @@ struct RespArgs {
     long off, n_out;      // outputs of this launch: out[off, off + n_out) (time-range shards)
     int Q, B;             // partitions; output blocks
     int nz;               // windows (forward workgroups)
-    const double2* tw;    // W_F^k, k < kH
+    const double2 *twf, *twi;   // the forward / inverse twiddles in thread order ([kTwRows][kThreads])
     double2* Z;           // [Q + B - 1 (+ pad)][kH] window spectra
     double* Zn;           // [..] their bin kH
     const double2* Y;     // [ys][B][kH] output spectra (bins < kH): ys partial sums over the partitions
@@ -326,7 +328,7 @@ __global__ __launch_bounds__(kThreads) void resp_fwd_kernel(RespArgs a, hz_modal
             }
             return make_double2(resp_u(a, m0 + mm), resp_u(a, m0 + mm + 1));
         },
-        a.tw, a.Z + (long)blockIdx.x * kH, a.Zn + blockIdx.x, true);
+        a.twf, a.Z + (long)blockIdx.x * kH, a.Zn + blockIdx.x, true);
 }
 
 // Y_b[q] = sum_{p < Q} H_p[q] Z_{b+Q-1-p}[q] for b in [b0, b0 + R): thread = bin q x R output
@@ -418,6 +420,9 @@ __global__ __launch_bounds__(256) void resp_mac_kernel(const double2* __restrict
 // FMAs in the same order, so the same bits) from LDS.  The register-only kernel loads every H row
 // once per 8 blocks and every Z row about four times: 55 MB through the L2s per C2 call, which its
 // operand phase waits 3.4 us for (stamps, profiles/r5/diag); here 20 MB.
+// (Of those 20 MB only 10 are fetched: the 8 block groups of a bin group run on one XCD, so their
+// re-reads hit its L2.  Tiles of 16 bins x 128 blocks and 8 x 256, which load every row once per
+// workgroup, measured level and 0.5 us slower per C2 launch: DESIGN.md 3.6.)
 constexpr int kMacBins = 64;
 // kMacBpw output blocks per wave, 4 waves: 32 blocks per workgroup (4 per wave -- 16 per workgroup,
 // twice the workgroups -- measured slower: 8.25 against 6.07 us per C2 launch,
@@ -723,7 +728,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) v
         const int k = t + i * kThreads;
         ya[i] = y[k];
         yb[i] = y[(kH - k) & (kH - 1)];   // k = 0: replaced by (Y_kH, 0) below
-        w[i] = a.tw[k];
+        w[i] = a.twi[(hz2k::kTwSlots + i) * kThreads + t];   // W^k
     }
     double2 ym = y[kH / 2];
     for (int sp = 1; sp < a.ys; ++sp) {   // the split MAC's partial sums, in split order
@@ -739,7 +744,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) v
         ym = make_double2(ym.x + um.x, ym.y + um.y);
     }
     hz2k::InvTw it;
-    it.load(a.tw);
+    it.load(a.twi);
     const UpkeepPre up = a.upkeep ? resp_upkeep_pre(a, b) : UpkeepPre();
     // bin kH (real): sum_p Hn[p] Zn[b + Q - 1 - p], wave 0 in a fixed order
     double yn = 0.0;
@@ -897,8 +902,19 @@ int resp_setup(hz_fb* h) {
             const long double ang = -2.0L * pi * k / kF;
             tw[k] = make_double2((double)cosl(ang), (double)sinl(ang));
         }
-        HZ_TRY(R.d_tw.reserve(2 * tw.size()));
-        HZ_TRY_HIP(hipMemcpy(R.d_tw, tw.data(), sizeof(double2) * tw.size(), hipMemcpyHostToDevice));
+        // the transforms read them in thread order (hz_fft2k.h): slot s of thread t, copied
+        std::vector<double2> tab(2 * kTwRows * kThreads);
+        for (int t = 0; t < kThreads; ++t) {
+            for (int s = 0; s < hz2k::kTwSlots; ++s) {
+                tab[kTwFwd + s * kThreads + t] = tw[hz2k::FwdTw::at(s, t)];
+                tab[kTwInv + s * kThreads + t] = tw[hz2k::InvTw::at(s, t)];
+            }
+            for (int i = 0; i < 4; ++i)   // the split's and the merge's W^(t + 256 i)
+                tab[kTwFwd + (hz2k::kTwSlots + i) * kThreads + t] = tab[kTwInv + (hz2k::kTwSlots + i) * kThreads + t] =
+                    tw[t + i * kThreads];
+        }
+        HZ_TRY(R.d_tw.reserve(2 * tab.size()));
+        HZ_TRY_HIP(hipMemcpy(R.d_tw, tab.data(), sizeof(double2) * tab.size(), hipMemcpyHostToDevice));
     }
     return HZ_OK;
 }
@@ -931,7 +947,7 @@ int resp_build_h(hz_fb* h) {
     if (R.over_valid)   // the whole bank's response (time-range shards)
         HZ_TRY_HIP(hipMemcpyAsync(R.d_h, R.h_over.data(), sizeof(double) * K, hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(resp_hspec_kernel, dim3((unsigned)Q), dim3(kThreads), 0, h->stream, (const double*)R.d_h, K,
-                       (const double2*)R.d_tw.get(), (double2*)R.d_H.get(), R.d_H + (size_t)Qp * 2 * kH);
+                       (const double2*)R.d_tw.get() + kTwFwd, (double2*)R.d_H.get(), R.d_H + (size_t)Qp * 2 * kH);
     HZ_TRY_HIP(hipGetLastError());
     if (col_q_ok(Q)) {   // the column path's partition spectra, lane order
         HZ_TRY(R.d_Hc.reserve((size_t)hz_col::kSlots * Q * 64 * 2));
@@ -1214,9 +1230,9 @@ int fb_launch_resp(hz_fb* h, const double* d_in, double* d_out, long n) {
     }
     const int B = (int)std::max<long>(1, (n_out + kP - 1) / kP);
     const int nz = Q + B - 1;
-    // rows the MAC may read: its last register window (B padded to kMacR output blocks, Qp
-    // partitions); rows past nz are never stored, only multiplied into discarded outputs
-    const int zrows = (B + 64 - 1) / 64 * 64 + Qp;
+    // rows the MAC may read: its last tile (B padded to the long-horizon kernel's 128 output blocks,
+    // Qp partitions); rows past nz are never stored, only multiplied into discarded outputs
+    const int zrows = (B + 128 - 1) / 128 * 128 + Qp;
     if ((size_t)zrows * (2 * kH + 1) > R.d_Z.cap()) {
         HZ_TRY(R.d_Z.reserve((size_t)zrows * (2 * kH + 1)));
         HZ_TRY_HIP(hipMemsetAsync(R.d_Z, 0, sizeof(double) * R.d_Z.cap(), h->stream));
@@ -1239,7 +1255,8 @@ int fb_launch_resp(hz_fb* h, const double* d_in, double* d_out, long n) {
     a.n_out = n_out;
     a.Q = Q;
     a.B = B;
-    a.tw = (const double2*)R.d_tw.get();
+    a.twf = (const double2*)R.d_tw.get() + kTwFwd;
+    a.twi = (const double2*)R.d_tw.get() + kTwInv;
     a.Z = (double2*)R.d_Z.get();
     a.Zn = R.d_Z + zn_at;
     a.Y = (const double2*)R.d_Y.get();
@@ -1440,7 +1457,7 @@ int fb_resp_tail_spectra(hz_fb* h, long K1) {
     HZ_TRY(S.d_tH.reserve((size_t)Qp * (2 * kH + 1)));
     HZ_TRY_HIP(hipMemsetAsync(S.d_tH, 0, sizeof(double) * (size_t)Qp * (2 * kH + 1), h->stream));
     hipLaunchKernelGGL(resp_hspec_kernel, dim3((unsigned)Q), dim3(kThreads), 0, h->stream, (const double*)(R.d_h + K1),
-                       Kt, (const double2*)R.d_tw.get(), (double2*)S.d_tH.get(), S.d_tH + (size_t)Qp * 2 * kH);
+                       Kt, (const double2*)R.d_tw.get() + kTwFwd, (double2*)S.d_tH.get(), S.d_tH + (size_t)Qp * 2 * kH);
     HZ_TRY_HIP(hipGetLastError());
     S.tQ = Q;
     return HZ_OK;
@@ -1468,7 +1485,8 @@ int fb_resp_tail_conv(hz_fb* h, const double* u, long n, double* out, hipStream_
     a.Q = Q;
     a.B = B;
     a.nz = nz;
-    a.tw = (const double2*)R.d_tw.get();
+    a.twf = (const double2*)R.d_tw.get() + kTwFwd;
+    a.twi = (const double2*)R.d_tw.get() + kTwInv;
     a.Z = (double2*)S.d_tZ.get();
     a.Zn = S.d_tZ + (size_t)zrows * 2 * kH;
     a.Y = (const double2*)S.d_tY.get();

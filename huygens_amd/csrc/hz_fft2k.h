@@ -5,7 +5,7 @@
 // twc) measured ~2 us per radix-8 pass for a lone workgroup on a CU (scripts/probe/
 // fft_phase_probe.hip): every instruction's latency is exposed at one wave per SIMD, and the
 // table lookups sit on each butterfly's critical path.  Here every pass is a compile-time
-// instance, its stage twiddles are loaded from the L2-resident W_4096 table at kernel start
+// instance, its stage twiddles are loaded from a thread-order table at kernel start
 // together with the data (one memory latency for everything), and the first forward / last
 // inverse pass run on registers: their groups are exactly the 8 points t + 256 i a thread loads
 // or stores.
@@ -43,19 +43,21 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
-// W_2048^m from the W_4096 table (tw[k] = e^{-2 pi i k / 4096}, k < 2048)
-__device__ __forceinline__ double2 w2k(const double2* __restrict__ tw, int m) { return tw[2 * m]; }
+// Stage twiddles: W_2048^m = tw[2 m] of the W_4096 table (tw[k] = e^{-2 pi i k / 4096}, k < 2048).
+// A thread's twiddles depend on threadIdx.x alone, and gathered from that table they are scattered
+// (pass (3, 8): 64 lanes on 64 different 128-byte lines), so the kernels read them from tables in
+// THREAD ORDER, built once at setup from the same values: table[slot][t], kTwSlots stage twiddles
+// (FwdTw::at / InvTw::at give slot s of thread t as an index into tw) and then the caller's own
+// slots (the split / merge twiddles) -- every load one contiguous 4 KB read per workgroup.
+constexpr int kTwSlots = 10;
 
 // ---- forward (DIF) -------------------------------------------------------------------------
 template <int R, int LH>
 struct Dif {
     static constexpr int LD = LH - (R - 1), M = 1 << R;
-    // stage twiddles of group b: W^(p << (kLg - 1 - LH + k)), k < R
-    static __device__ __forceinline__ void load_tw(double2 (&w)[R], int b, const double2* __restrict__ tw) {
-        const int p = b & ((1 << LD) - 1);
-#pragma unroll
-        for (int k = 0; k < R; ++k) w[k] = LD == 0 ? make_double2(1.0, 0.0) : w2k(tw, p << (kLg - 1 - LH + k));
-    }
+    // stage twiddle k < R of group b: W^(p << (kLg - 1 - LH + k)), as an index into tw (LD == 0: all
+    // ones, a compile-time constant in regs)
+    static constexpr int tw_at(int b, int k) { return 2 * ((b & ((1 << LD) - 1)) << (kLg - 1 - LH + k)); }
     static __device__ __forceinline__ void regs(double* xr, double* xi, const double2 (&w)[R]) {
 #pragma unroll
         for (int k = 0; k < R; ++k) {
@@ -94,12 +96,23 @@ struct Dif {
 // every twiddle of a thread's forward transform, loaded at kernel start
 struct FwdTw {
     double2 p1[2][2], p2[3], p3[3];
-    __device__ __forceinline__ void load(const double2* __restrict__ tw) {
-        const int t = threadIdx.x;
-        Dif<2, 10>::load_tw(p1[0], t, tw);
-        Dif<2, 10>::load_tw(p1[1], t + kT, tw);
-        Dif<3, 8>::load_tw(p2, t, tw);
-        Dif<3, 5>::load_tw(p3, t, tw);
+    // slots: p1[0][0..1], p1[1][0..1] (groups t and t + 256 of the register pass), p2[0..2], p3[0..2]
+    static constexpr int at(int s, int t) {
+        return s < 2 ? Dif<2, 10>::tw_at(t, s) : s < 4 ? Dif<2, 10>::tw_at(t + kT, s - 2)
+             : s < 7 ? Dif<3, 8>::tw_at(t, s - 4) : Dif<3, 5>::tw_at(t, s - 7);
+    }
+    __device__ __forceinline__ void load(const double2* __restrict__ tab) {
+        const double2* c = tab + threadIdx.x;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            p1[0][k] = c[k * kT];
+            p1[1][k] = c[(2 + k) * kT];
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            p2[k] = c[(4 + k) * kT];
+            p3[k] = c[(7 + k) * kT];
+        }
     }
 };
 
@@ -141,12 +154,9 @@ __device__ __forceinline__ void fwd(Lds& s, double (&vr)[kPT], double (&vi)[kPT]
 template <int R, int LH>
 struct Dit {
     static constexpr int M = 1 << R;
-    // stage twiddles of group b: conj W^(p << (kLg - 1 - LH - k)), k < R
-    static __device__ __forceinline__ void load_tw(double2 (&w)[R], int b, const double2* __restrict__ tw) {
-        const int p = b & ((1 << LH) - 1);
-#pragma unroll
-        for (int k = 0; k < R; ++k) w[k] = LH == 0 ? make_double2(1.0, 0.0) : w2k(tw, p << (kLg - 1 - LH - k));
-    }
+    // stage twiddle k < R of group b: conj W^(p << (kLg - 1 - LH - k)), as an index into tw (LH == 0:
+    // all ones, a compile-time constant in regs)
+    static constexpr int tw_at(int b, int k) { return 2 * ((b & ((1 << LH) - 1)) << (kLg - 1 - LH - k)); }
     static __device__ __forceinline__ void regs(double* xr, double* xi, const double2 (&w)[R]) {
 #pragma unroll
         for (int k = 0; k < R; ++k) {
@@ -184,12 +194,23 @@ struct Dit {
 
 struct InvTw {
     double2 p2[3], p3[3], p4[2][2];
-    __device__ __forceinline__ void load(const double2* __restrict__ tw) {
-        const int t = threadIdx.x;
-        Dit<3, 3>::load_tw(p2, t, tw);
-        Dit<3, 6>::load_tw(p3, t, tw);
-        Dit<2, 9>::load_tw(p4[0], t, tw);
-        Dit<2, 9>::load_tw(p4[1], t + kT, tw);
+    // slots: p2[0..2], p3[0..2], p4[0][0..1], p4[1][0..1] (groups t and t + 256 of the register pass)
+    static constexpr int at(int s, int t) {
+        return s < 3 ? Dit<3, 3>::tw_at(t, s) : s < 6 ? Dit<3, 6>::tw_at(t, s - 3)
+             : s < 8 ? Dit<2, 9>::tw_at(t, s - 6) : Dit<2, 9>::tw_at(t + kT, s - 8);
+    }
+    __device__ __forceinline__ void load(const double2* __restrict__ tab) {
+        const double2* c = tab + threadIdx.x;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            p2[k] = c[k * kT];
+            p3[k] = c[(3 + k) * kT];
+        }
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            p4[0][k] = c[(6 + k) * kT];
+            p4[1][k] = c[(8 + k) * kT];
+        }
     }
 };
 

@@ -13,7 +13,7 @@ from .delay import Delay, Delaybank  # noqa: F401
 from .stft import Cosine, Fourier, StaticSTFT  # noqa: F401
 from .granulator import GRAIN_REQ, Granulator  # noqa: F401
 from .freezer import Freezer  # noqa: F401
-from .heterodyne import Heterodyne, harmbank  # noqa: F401
+from .heterodyne import Heterodyne, StickChain, harmbank, phasebank  # noqa: F401
 from .subtractive import Subtractive  # noqa: F401
 
-__all__ = ["HZError", "load", "header_symbols", "Filterbank", "sample_many", "Oscbank", "Additive", "Sinusoids", "GRAV_TRUNC", "GRAV_FABS", "Bowl", "Delay", "Delaybank", "Fourier", "StaticSTFT", "Cosine", "Granulator", "GRAIN_REQ", "Freezer", "Heterodyne", "harmbank", "Subtractive"]
+__all__ = ["HZError", "load", "header_symbols", "Filterbank", "sample_many", "Oscbank", "Additive", "Sinusoids", "GRAV_TRUNC", "GRAV_FABS", "Bowl", "Delay", "Delaybank", "Fourier", "StaticSTFT", "Cosine", "Granulator", "GRAIN_REQ", "Freezer", "Heterodyne", "StickChain", "harmbank", "phasebank", "Subtractive"]

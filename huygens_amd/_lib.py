@@ -258,6 +258,10 @@ _SIGS = {
     "hz_gran_profile_read": (I, [VP, PD, C.POINTER(L), C.POINTER(L)]),
     # heterodyne chain
     "hz_het_create": (I, [I, I, PD, D, D, C.c_uint, I, D, D, D, I, C.POINTER(VP)]),
+    "hz_het_create_phase": (I, [I, I, PD, D, D, C.c_uint, I, D, D, D, I, C.POINTER(VP)]),
+    "hz_het_create_sticks": (I, [I, I, I, D, D, D, D, I, C.POINTER(VP)]),
+    "hz_het_chain": (I, [VP, C.POINTER(I)]),
+    "hz_het_set_output": (I, [VP, I, D, D]),
     "hz_het_destroy": (I, [VP]),
     "hz_het_setup": (I, [VP, I, PD]),
     "hz_het_freqmod": (I, [VP, I, C.POINTER(I), PD, I]),

@@ -25,6 +25,15 @@
 // RMSbank history ring [width + 1][Np] (slot-major, so the 64 lanes of a wave read and
 // write one contiguous 512 B row per sample); per-group partial mixes [G][chunk].
 // Algorithmic traffic per channel-sample: the ring's one read + one write (16 B).
+//
+// Two more chains share the layout, the mix rounds and the oscillator tick:
+//   PHASE  (tests/phasebank.cpp:77-101, het_phase_kernel): the latched signal splits into a
+//          magnitude path (Distbank(&length)) and a phase path (Distbank(&angle) into the
+//          Stickbank), recombined by a third Modbank before demodulation.
+//   STICKS (tests/oscbank.cpp:106-110, het_sticks_kernel): modulate, `pre` cascaded order-1
+//          Stickbanks, Distbank(&gate), `post` more, demodulate; no Slidebank, ring or latch.
+// het_mix_kernel's output stage covers the three programs' tails: limiter or none, and
+// tests/slidebank.cpp:95's softclip(drive mix) in front of the gain.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -72,6 +81,7 @@ struct HetArgs {
     double lo, hi;         // thresh * ratio, thresh * (1 - ratio)
     double width, sgain;   // (double)width; pow(1 + rad, stick_order)
     double back[kMaxStick];
+    double gate;           // STICKS: Distbank(&gate) threshold (<= 0: no Distbank)
 };
 
 // The two quotients r / nrm and m / nrm share one reciprocal.  This is the f64 divide's own
@@ -283,7 +293,315 @@ chain_fn chain_kernel(int order, int sorder, bool pref) {
     }
 }
 
-// out[t] = limiter(dry x[t] + gain mix[t]); mix[t] = four strided slices of the group rows
+// latchbank.h:83-93, one call
+__device__ __forceinline__ void latch_update(bool& armed, bool& engaged, double rms, double lo, double hi) {
+    armed = armed || rms < lo;
+    const bool t1 = engaged && rms < lo;
+    const bool t2 = !engaged && rms > hi && armed;
+    engaged = engaged && !t1;
+    armed = armed && !t1;
+    engaged = engaged || t2;
+}
+
+// The PHASE chain (tests/phasebank.cpp:77-101): het_chain_kernel's sibling -- same layout, ring,
+// mix rounds and ticks; between the Slidebank and the demodulation the signal runs
+//     phase_combiners(absbank(latchbank(&rmsbank, s)), smoothbank(argbank(latchbank(&rmsbank, s))))
+// Two quirks of the reference are kept:
+//  * The Latchbank is called twice per sample.  The argument order of phase_combiners(...) is
+//    unspecified in C++; clang (the author's build) evaluates left to right, so
+//    the magnitude path takes the first latch update and the phase path the second.  The second
+//    RMSbank call finds `computed` set and only re-applies *out = sqrt(*out / width)
+//    (rmsbank.h:56-65), so the second update sees sqrt(rms / width), not rms.  The stored latch
+//    state is the one after both updates.
+//  * A disengaged channel passes s * 0.0 = (+-0, +-0) with the signs of s, and atan2(+-0, -0)
+//    is +-pi: the phase path sees +-pi while the channel is silent and the Stickbank carries it
+//    into the engaged stretch that follows.  There is no shortcut to P = 0.
+// The smoothbank state and the output pass through device hypot / atan2 (not libm's); every
+// other state is bit-exact as in het_chain_kernel.
+template <int O, int S, bool PREF>
+__global__ __launch_bounds__(kThreads, 24) void het_phase_kernel(HetArgs a) {
+    __shared__ double buf[kCH * kRow];
+    __shared__ double xs[kCH];
+    const int tid = threadIdx.x;
+    const long c = (long)blockIdx.x * kThreads + tid;
+    const long Np = a.Np;
+    double* st = a.st + c;
+    double zar = st[F_ZAR * Np], zai = st[F_ZAI * Np];
+    const double war = st[F_WAR * Np], wai = st[F_WAI * Np];
+    double zsr = st[F_ZSR * Np], zsi = st[F_ZSI * Np];
+    const double wsr = st[F_WSR * Np], wsi = st[F_WSI * Np];
+    const double rr = st[F_RR * Np], ri = st[F_RI * Np];
+    double rsum = st[F_RSUM * Np];
+    double slr[O], sli[O], ykr[S], yki[S];
+#pragma unroll
+    for (int q = 0; q < O; ++q) {
+        slr[q] = st[(F_SLIDE + 2 * q) * Np];
+        sli[q] = st[(F_SLIDE + 2 * q + 1) * Np];
+    }
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        ykr[k] = st[(F_STICK + 2 * k) * Np];
+        yki[k] = st[(F_STICK + 2 * k + 1) * Np];
+    }
+    const bool act_a = a.act[c] != 0, act_s = a.act[Np + c] != 0;
+    bool armed = (a.latch[c] & 1) != 0, engaged = (a.latch[c] & 2) != 0;
+    const bool live = c < a.N;
+    const double cr = 1.0 - rr, ci = 0.0 - ri;   // std::complex(1, 0) - radii (slidebank.h:77)
+    const double lo = a.lo, hi = a.hi, width = a.width, sgain = a.sgain;
+    double* ring = a.ring + c;
+    const unsigned W1 = a.W1;
+    unsigned sw = a.r0;
+    unsigned sr = sw == 0 ? W1 - 1 : sw - 1;
+    double pre[kDist];
+    if constexpr (PREF) {
+#pragma unroll
+        for (int d = 0; d < kDist; ++d) {
+            pre[d] = ring[(long)sr * Np];   // slots are always in range; values past n are unused
+            sr = sr == 0 ? W1 - 1 : sr - 1;
+        }
+    }
+    double* bcol = buf + (tid / kRunLen) * kRun + tid % kRunLen;   // this channel's column
+    for (long t0 = 0; t0 < a.n; t0 += kCH) {
+        const int m = (int)min((long)kCH, a.n - t0);
+        if (tid < m) xs[tid] = a.x[t0 + tid];
+        __syncthreads();   // xs ready; the previous round's buf reads done
+        for (int j = 0; j < m; ++j) {
+            double old;
+            if constexpr (PREF) {
+                old = pre[0];
+#pragma unroll
+                for (int d = 0; d + 1 < kDist; ++d) pre[d] = pre[d + 1];
+                pre[kDist - 1] = ring[(long)sr * Np];
+            } else {
+                old = ring[(long)sr * Np];
+            }
+            sr = sr == 0 ? W1 - 1 : sr - 1;
+            const double x = xs[j];
+            // modulators(x, analysis()); slidebank: as het_chain_kernel
+            double inr = x * zar, ini = x * zai;
+#pragma unroll
+            for (int q = 0; q < O; ++q) {
+                const double ar = cr * inr - ci * ini, ai = cr * ini + ci * inr;
+                const double br = rr * slr[q] - ri * sli[q], bi = rr * sli[q] + ri * slr[q];
+                inr = slr[q];
+                ini = sli[q];
+                slr[q] = ar + br;
+                sli[q] = ai + bi;
+            }
+            const double sre = slr[O - 1], sim = sli[O - 1];
+            const double a2 = sre * sre + sim * sim;
+            ring[(long)sw * Np] = a2;
+            sw = sw == 0 ? W1 - 1 : sw - 1;
+            rsum = a2 - old + rsum;
+            // absbank(latchbank(&rmsbank, slidebank())): the first latch update, |l1| as (A, +0)
+            const double r1 = sqrt(rsum / width);
+            latch_update(armed, engaged, r1, lo, hi);
+            const double e1 = engaged ? 1.0 : 0.0;
+            const double A = hypot(sre * e1, sim * e1);
+            // argbank(latchbank(&rmsbank, slidebank())): the second update sees sqrt(r1 / width);
+            // arg(l2) as (P, +0), +-pi for a silent channel whose s has a negative real part
+            const double r2 = sqrt(r1 / width);
+            latch_update(armed, engaged, r2, lo, hi);
+            const double e2 = engaged ? 1.0 : 0.0;
+            const double P = atan2(sim * e2, sre * e2);
+            // smoothbank on (P, 0): y = (1 + rad)^order (P, 0) - block * back
+            double accr = 0.0, acci = 0.0;
+#pragma unroll
+            for (int k = 0; k < S; ++k) {
+                const double pr = ykr[k] * a.back[k] - yki[k] * 0.0, pi = ykr[k] * 0.0 + yki[k] * a.back[k];
+                accr = accr + pr;
+                acci = acci + pi;
+            }
+            const double yr = sgain * P - accr, yi = sgain * 0.0 - acci;
+#pragma unroll
+            for (int k = S - 1; k > 0; --k) {
+                ykr[k] = ykr[k - 1];
+                yki[k] = yki[k - 1];
+            }
+            ykr[0] = yr;
+            yki[0] = yi;
+            // phase_combiners((A, 0), y) (Eigen's complex product), then demodulators(synthesis(), .)
+            const double cre = A * yr - 0.0 * yi, cim = A * yi + 0.0 * yr;
+            const double dr = zsr * cre - zsi * cim;
+            bcol[j * kRow] = live ? dr : 0.0;
+            if (act_a) osc_tick(zar, zai, war, wai);
+            if (act_s) osc_tick(zsr, zsi, wsr, wsi);
+        }
+        __syncthreads();   // buf complete
+        {
+            const int j = tid / kLanes, p = tid % kLanes;   // kLanes lanes per sample: run p
+            double s = 0.0;
+            if (j < m) {
+                const double* row = buf + j * kRow + p * kRun;
+#pragma unroll
+                for (int k = 0; k < kRunLen; ++k) s += row[k];
+            }
+#pragma unroll
+            for (int w = 1; w < kLanes; w <<= 1) s += __shfl_xor(s, w);
+            if (p == 0 && j < m) a.part[blockIdx.x * a.pstride + t0 + j] = s;
+        }
+    }
+    st[F_ZAR * Np] = zar;
+    st[F_ZAI * Np] = zai;
+    st[F_ZSR * Np] = zsr;
+    st[F_ZSI * Np] = zsi;
+    st[F_RSUM * Np] = rsum;
+#pragma unroll
+    for (int q = 0; q < O; ++q) {
+        st[(F_SLIDE + 2 * q) * Np] = slr[q];
+        st[(F_SLIDE + 2 * q + 1) * Np] = sli[q];
+    }
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        st[(F_STICK + 2 * k) * Np] = ykr[k];
+        st[(F_STICK + 2 * k + 1) * Np] = yki[k];
+    }
+    a.latch[c] = (unsigned char)((armed ? 1 : 0) | (engaged ? 2 : 0));
+}
+
+template <int O, int S>
+constexpr chain_fn phase_pick(bool pref) {
+    return pref ? het_phase_kernel<O, S, true> : het_phase_kernel<O, S, false>;
+}
+
+template <int S>
+chain_fn phase_for_order(int order, bool pref) {
+    switch (order) {
+    case 1: return phase_pick<1, S>(pref);
+    case 2: return phase_pick<2, S>(pref);
+    case 3: return phase_pick<3, S>(pref);
+    case 4: return phase_pick<4, S>(pref);
+    case 5: return phase_pick<5, S>(pref);
+    case 6: return phase_pick<6, S>(pref);
+    case 7: return phase_pick<7, S>(pref);
+    default: return phase_pick<8, S>(pref);
+    }
+}
+
+chain_fn phase_kernel(int order, int sorder, bool pref) {
+    switch (sorder) {
+    case 1: return phase_for_order<1>(order, pref);
+    case 2: return phase_for_order<2>(order, pref);
+    case 3: return phase_for_order<3>(order, pref);
+    default: return phase_for_order<4>(order, pref);
+    }
+}
+
+// The STICKS chain (tests/oscbank.cpp:106-110): modbank1(x, oscbank1()), PRE cascaded
+// Stickbank(1, rad), Distbank(&gate) (gate > 0), POST more, modbank2(oscbank2(), .), Mixer.  Each
+// Stickbank keeps its own tap y = (1 + rad) in - y_prev rad (stickbank.h:189 at order 1, spelt
+// as het_chain_kernel's S = 1 case); a cascade of k of them rounds differently from one order-k
+// bank.  No Slidebank, ring or latch.  Taps live in the F_STICK fields, pre first.
+template <int PRE, int POST>
+__global__ __launch_bounds__(kThreads) void het_sticks_kernel(HetArgs a) {
+    static_assert(PRE + POST >= 1 && PRE + POST <= kMaxStick, "one to kMaxStick Stickbanks");
+    constexpr int K = PRE + POST;
+    __shared__ double buf[kCH * kRow];
+    __shared__ double xs[kCH];
+    const int tid = threadIdx.x;
+    const long c = (long)blockIdx.x * kThreads + tid;
+    const long Np = a.Np;
+    double* st = a.st + c;
+    double zar = st[F_ZAR * Np], zai = st[F_ZAI * Np];
+    const double war = st[F_WAR * Np], wai = st[F_WAI * Np];
+    double zsr = st[F_ZSR * Np], zsi = st[F_ZSI * Np];
+    const double wsr = st[F_WSR * Np], wsi = st[F_WSI * Np];
+    double ykr[K], yki[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        ykr[k] = st[(F_STICK + 2 * k) * Np];
+        yki[k] = st[(F_STICK + 2 * k + 1) * Np];
+    }
+    const bool act_a = a.act[c] != 0, act_s = a.act[Np + c] != 0;
+    const bool live = c < a.N;
+    const double sgain = a.sgain, back = a.back[0], gate = a.gate;
+    const bool gated = gate > 0.0;
+    auto stick = [&](int k, double& vr, double& vi) {
+        const double pr = ykr[k] * back - yki[k] * 0.0, pi = ykr[k] * 0.0 + yki[k] * back;
+        const double accr = 0.0 + pr, acci = 0.0 + pi;
+        vr = sgain * vr - accr;
+        vi = sgain * vi - acci;
+        ykr[k] = vr;
+        yki[k] = vi;
+    };
+    double* bcol = buf + (tid / kRunLen) * kRun + tid % kRunLen;   // this channel's column
+    for (long t0 = 0; t0 < a.n; t0 += kCH) {
+        const int m = (int)min((long)kCH, a.n - t0);
+        if (tid < m) xs[tid] = a.x[t0 + tid];
+        __syncthreads();   // xs ready; the previous round's buf reads done
+        for (int j = 0; j < m; ++j) {
+            const double x = xs[j];
+            double vr = x * zar, vi = x * zai;
+#pragma unroll
+            for (int k = 0; k < PRE; ++k) stick(k, vr, vi);
+            // gate(x) = abs(x) < gate ? 0 : x (oscbank.cpp:48-51)
+            if (gated && hypot(vr, vi) < gate) vr = vi = 0.0;
+#pragma unroll
+            for (int k = PRE; k < K; ++k) stick(k, vr, vi);
+            const double dr = zsr * vr - zsi * vi;
+            bcol[j * kRow] = live ? dr : 0.0;
+            if (act_a) osc_tick(zar, zai, war, wai);
+            if (act_s) osc_tick(zsr, zsi, wsr, wsi);
+        }
+        __syncthreads();   // buf complete
+        {
+            const int j = tid / kLanes, p = tid % kLanes;   // kLanes lanes per sample: run p
+            double s = 0.0;
+            if (j < m) {
+                const double* row = buf + j * kRow + p * kRun;
+#pragma unroll
+                for (int k = 0; k < kRunLen; ++k) s += row[k];
+            }
+#pragma unroll
+            for (int w = 1; w < kLanes; w <<= 1) s += __shfl_xor(s, w);
+            if (p == 0 && j < m) a.part[blockIdx.x * a.pstride + t0 + j] = s;
+        }
+    }
+    st[F_ZAR * Np] = zar;
+    st[F_ZAI * Np] = zai;
+    st[F_ZSR * Np] = zsr;
+    st[F_ZSI * Np] = zsi;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        st[(F_STICK + 2 * k) * Np] = ykr[k];
+        st[(F_STICK + 2 * k + 1) * Np] = yki[k];
+    }
+}
+
+template <int PRE, int POST>
+constexpr chain_fn sticks_pick() {
+    if constexpr (PRE + POST >= 1 && PRE + POST <= kMaxStick)
+        return het_sticks_kernel<PRE, POST>;
+    else
+        return nullptr;
+}
+
+template <int PRE>
+chain_fn sticks_for_post(int post) {
+    switch (post) {
+    case 0: return sticks_pick<PRE, 0>();
+    case 1: return sticks_pick<PRE, 1>();
+    case 2: return sticks_pick<PRE, 2>();
+    case 3: return sticks_pick<PRE, 3>();
+    case 4: return sticks_pick<PRE, 4>();
+    default: return nullptr;
+    }
+}
+
+chain_fn sticks_kernel(int pre, int post) {
+    switch (pre) {
+    case 0: return sticks_for_post<0>(post);
+    case 1: return sticks_for_post<1>(post);
+    case 2: return sticks_for_post<2>(post);
+    case 3: return sticks_for_post<3>(post);
+    case 4: return sticks_for_post<4>(post);
+    default: return nullptr;
+    }
+}
+
+// out[t] = shaper(dry x[t] + gain v[t]), v = mix[t] or, with drive != 0, softclip(drive mix[t],
+// clip) (tests/slidebank.cpp:81-95); shaper = the limiter or none (tests/oscbank.cpp:106).
+// mix[t] = four strided slices of the group rows
 // (g = sl mod 4, in order), added in slice order: fixed, deterministic.  64 samples x 4
 // slices per block, so a launch has n / 64 blocks and each lane streams G / 4 rows.
 constexpr int kMixSamples = 64, kMixSlices = 4;
@@ -292,7 +610,8 @@ __global__ __launch_bounds__(kMixSamples* kMixSlices) void het_mix_kernel(const 
                                                                         const double* __restrict__ part,
                                                                         double* __restrict__ out, long n,
                                                                         long pstride, int G, double dry,
-                                                                        double gain) {
+                                                                        double gain, int shaper, double drive,
+                                                                        double clip) {
     __shared__ double red[kMixSlices][kMixSamples];
     const int s = threadIdx.x % kMixSamples, sl = threadIdx.x / kMixSamples;
     const long t = (long)blockIdx.x * kMixSamples + s;
@@ -307,7 +626,10 @@ __global__ __launch_bounds__(kMixSamples* kMixSlices) void het_mix_kernel(const 
         double mix = red[0][s];
 #pragma unroll
         for (int k = 1; k < kMixSlices; ++k) mix += red[k][s];
-        out[t] = hz::dist_apply<HZ_DIST_LIMITER>(dry * x[t] + gain * mix, 0.0);
+        // drive 0: the expression below is limiter(dry x + gain mix), as without an output stage
+        if (drive != 0.0) mix = hz::dist_apply<HZ_DIST_SOFTCLIP>(drive * mix, clip);
+        const double v = dry * x[t] + gain * mix;
+        out[t] = shaper == HZ_HET_OUT_RAW ? v : hz::dist_apply<HZ_DIST_LIMITER>(v, 0.0);
     }
 }
 
@@ -316,6 +638,11 @@ __global__ __launch_bounds__(kMixSamples* kMixSlices) void het_mix_kernel(const 
 struct hz_het {
     hz::Stream stream;
     int N = 0, order = 1, sorder = 1, device = 0;
+    int chain = HZ_HET_CHAIN_HARM;
+    int pre = 0, post = 0;                // STICKS: Stickbanks before / after the gate
+    double gate = 0;                      // STICKS: Distbank(&gate) threshold (<= 0: none)
+    int shaper = HZ_HET_OUT_LIMITER;      // output stage (hz_het_set_output)
+    double drive = 0, clip = 0;
     long Np = 0, G = 0;
     unsigned width = 0, W1 = 1, r = 0;   // RMSbank origin (decrements per sample)
     double thresh = 0, ratio = 0, dry = 0, gain = 0, sgain = 1;
@@ -425,13 +752,17 @@ int het_run(hz_het* h, const double* d_in, double* d_out, long n) {
         a.width = (double)h->width;
         a.sgain = h->sgain;
         for (int k = 0; k < kMaxStick; ++k) a.back[k] = h->back[k];
+        a.gate = h->gate;
+        const bool pref = h->width > (unsigned)kDist;
+        const chain_fn fn = h->chain == HZ_HET_CHAIN_STICKS  ? sticks_kernel(h->pre, h->post)
+                            : h->chain == HZ_HET_CHAIN_PHASE ? phase_kernel(h->order, h->sorder, pref)
+                                                             : chain_kernel(h->order, h->sorder, pref);
         hipEvent_t* e = nullptr;
         if (h->prof) {
             HZ_TRY(h->ev.take(2, &e));
             HZ_TRY_HIP(hipEventRecord(e[0], h->stream));
         }
-        hipLaunchKernelGGL(chain_kernel(h->order, h->sorder, h->width > (unsigned)kDist), dim3((unsigned)h->G),
-                           dim3(kThreads), 0, h->stream, a);
+        hipLaunchKernelGGL(fn, dim3((unsigned)h->G), dim3(kThreads), 0, h->stream, a);
         HZ_TRY_HIP(hipGetLastError());
         if (e) {
             HZ_TRY_HIP(hipEventRecord(e[1], h->stream));
@@ -440,29 +771,23 @@ int het_run(hz_het* h, const double* d_in, double* d_out, long n) {
         }
         hipLaunchKernelGGL(het_mix_kernel, dim3((unsigned)((m + kMixSamples - 1) / kMixSamples)),
                            dim3(kMixSamples * kMixSlices), 0, h->stream, d_in + c0,
-                           (const double*)h->d_part, d_out + c0, m, h->chunk, (int)h->G, h->dry, h->gain);
+                           (const double*)h->d_part, d_out + c0, m, h->chunk, (int)h->G, h->dry, h->gain,
+                           h->shaper, h->drive, h->clip);
         HZ_TRY_HIP(hipGetLastError());
         h->r = (unsigned)(((long)h->r - m % h->W1 + h->W1) % h->W1);
     }
     return HZ_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int hz_het_create(int channels, int order, const double* radii, double thresh, double ratio, unsigned width,
-                  int stick_order, double stick_rad, double dry, double gain, int device, hz_het** out) {
-    if (!out || channels <= 0 || !radii || width == 0 || width > (1u << 24) || stick_order > kMaxStick ||
-        order > kMaxOrder) {
-        hz::set_error("hz_het_create: invalid arguments (channels > 0, radii, 0 < width <= 2^24, order <= %d, "
-                      "stick_order <= %d)", kMaxOrder, kMaxStick);
-        return HZ_E_INVALID;
-    }
+// the three create calls share this: STICKS has no Slidebank (radii null), ring or latch
+// thresholds (width 0: no ring is allocated)
+int het_create(int chain, int channels, int order, const double* radii, double thresh, double ratio, unsigned width,
+               int stick_order, double stick_rad, double dry, double gain, int device, hz_het** out) {
     *out = nullptr;
     HZ_TRY(hz::select_device(device));
     hz_het* h = new (std::nothrow) hz_het();
     if (!h) return HZ_E_ALLOC;
+    h->chain = chain;
     h->N = channels;
     h->Np = ((long)channels + kThreads - 1) / kThreads * kThreads;
     h->G = h->Np / kThreads;
@@ -484,15 +809,15 @@ int hz_het_create(int channels, int order, const double* radii, double thresh, d
     h->chunk = std::max(1L, std::min(1L << 20, kPartBytes / (long)sizeof(double) / h->G));
     if (const char* e = std::getenv("HZ_HET_CHUNK"))   // test hook: force launch splits
         h->chunk = std::max(1L, std::min(h->chunk, std::atol(e)));
-    const size_t ring_bytes = sizeof(double) * (size_t)h->W1 * h->Np;
+    const size_t ring_bytes = width == 0 ? 0 : sizeof(double) * (size_t)h->W1 * h->Np;
     bool ok = h->stream.create() == HZ_OK;
     ok = ok && h->d_st.reserve((size_t)F_COUNT * h->Np) == HZ_OK;
-    ok = ok && h->d_ring.reserve((size_t)h->W1 * h->Np) == HZ_OK;
+    ok = ok && (width == 0 || h->d_ring.reserve((size_t)h->W1 * h->Np) == HZ_OK);
     ok = ok && h->d_act.reserve(2 * (size_t)h->Np) == HZ_OK;
     ok = ok && h->d_latch.reserve(h->Np) == HZ_OK;
     ok = ok && h->d_part.reserve((size_t)h->G * h->chunk) == HZ_OK;
     ok = ok && hipMemset(h->d_st, 0, sizeof(double) * F_COUNT * h->Np) == hipSuccess;
-    ok = ok && hipMemset(h->d_ring, 0, ring_bytes) == hipSuccess;
+    ok = ok && (width == 0 || hipMemset(h->d_ring, 0, ring_bytes) == hipSuccess);
     ok = ok && hipMemset(h->d_act, 0, 2 * h->Np) == hipSuccess;
     ok = ok && hipMemset(h->d_latch, 0, h->Np) == hipSuccess;
     if (!ok) {
@@ -505,13 +830,80 @@ int hz_het_create(int channels, int order, const double* radii, double thresh, d
         int rc = HZ_OK;
         for (int f : {F_ZAR, F_WAR, F_ZSR, F_WSR})
             if (rc == HZ_OK) rc = upload_field(h, f, ones.data());
-        if (rc == HZ_OK) rc = het_setup(h, order, radii);
+        if (rc == HZ_OK && radii) rc = het_setup(h, order, radii);
+        if (rc == HZ_OK) rc = hz_het_synchronize(h);   // `ones` is stack-owned
         if (rc != HZ_OK) {
             hz_het_destroy(h);
             return rc;
         }
     }
     *out = h;
+    return HZ_OK;
+}
+
+bool harm_args_ok(int channels, const double* radii, unsigned width, int stick_order, int order, hz_het** out) {
+    return out && channels > 0 && radii && width != 0 && width <= (1u << 24) && stick_order <= kMaxStick &&
+           order <= kMaxOrder;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hz_het_create(int channels, int order, const double* radii, double thresh, double ratio, unsigned width,
+                  int stick_order, double stick_rad, double dry, double gain, int device, hz_het** out) {
+    if (!harm_args_ok(channels, radii, width, stick_order, order, out)) {
+        hz::set_error("hz_het_create: invalid arguments (channels > 0, radii, 0 < width <= 2^24, order <= %d, "
+                      "stick_order <= %d)", kMaxOrder, kMaxStick);
+        return HZ_E_INVALID;
+    }
+    return het_create(HZ_HET_CHAIN_HARM, channels, order, radii, thresh, ratio, width, stick_order, stick_rad, dry,
+                      gain, device, out);
+}
+
+int hz_het_create_phase(int channels, int order, const double* radii, double thresh, double ratio, unsigned width,
+                        int stick_order, double stick_rad, double dry, double gain, int device, hz_het** out) {
+    if (!harm_args_ok(channels, radii, width, stick_order, order, out)) {
+        hz::set_error("hz_het_create_phase: invalid arguments (channels > 0, radii, 0 < width <= 2^24, order <= %d, "
+                      "stick_order <= %d)", kMaxOrder, kMaxStick);
+        return HZ_E_INVALID;
+    }
+    return het_create(HZ_HET_CHAIN_PHASE, channels, order, radii, thresh, ratio, width, stick_order, stick_rad, dry,
+                      gain, device, out);
+}
+
+int hz_het_create_sticks(int channels, int pre, int post, double rad, double gate, double dry, double gain,
+                         int device, hz_het** out) {
+    if (!out || channels <= 0 || pre < 0 || post < 0 || pre + post < 1 || pre + post > kMaxStick) {
+        hz::set_error("hz_het_create_sticks: invalid arguments (channels > 0, pre, post >= 0, 1 <= pre + post <= %d)",
+                      kMaxStick);
+        return HZ_E_INVALID;
+    }
+    HZ_TRY(het_create(HZ_HET_CHAIN_STICKS, channels, 1, nullptr, 0.0, 0.0, 0, 1, rad, dry, gain, device, out));
+    (*out)->pre = pre;
+    (*out)->post = post;
+    (*out)->gate = gate;
+    (*out)->shaper = HZ_HET_OUT_RAW;   // oscbank.cpp:106: dry x + mix, no limiter
+    return HZ_OK;
+}
+
+int hz_het_chain(hz_het* h, int* chain) {
+    HZ_TRY(het_check(h));
+    if (!chain) return HZ_E_INVALID;
+    *chain = h->chain;
+    return HZ_OK;
+}
+
+int hz_het_set_output(hz_het* h, int shaper, double drive, double clip_width) {
+    HZ_TRY(het_check(h));
+    if ((shaper != HZ_HET_OUT_LIMITER && shaper != HZ_HET_OUT_RAW) || !std::isfinite(drive) ||
+        (drive != 0.0 && !(clip_width >= 0.0 && clip_width < 1.0))) {
+        hz::set_error("hz_het_set_output: shaper LIMITER or RAW, finite drive, 0 <= clip_width < 1");
+        return HZ_E_INVALID;
+    }
+    h->shaper = shaper;
+    h->drive = drive;
+    h->clip = clip_width;
     return HZ_OK;
 }
 
@@ -525,6 +917,10 @@ int hz_het_destroy(hz_het* h) {
 
 int hz_het_setup(hz_het* h, int order, const double* radii) {
     HZ_TRY(het_check(h));
+    if (h->chain == HZ_HET_CHAIN_STICKS) {
+        hz::set_error("hz_het_setup: the STICKS chain has no Slidebank");
+        return HZ_E_UNSUPPORTED;
+    }
     if (!radii) return HZ_E_INVALID;
     return het_setup(h, order, radii);
 }
@@ -585,6 +981,11 @@ int hz_het_process(hz_het* h, const double* in, double* out, size_t n) {
 int hz_het_state(hz_het* h, int what, double* dst) {
     HZ_TRY(het_check(h));
     if (!dst || what < 0 || what > HZ_HET_STATE_HISTORY) return HZ_E_INVALID;
+    const bool sticks = h->chain == HZ_HET_CHAIN_STICKS;
+    if (sticks && what != HZ_HET_STATE_ANALYSIS && what != HZ_HET_STATE_SYNTHESIS && what != HZ_HET_STATE_STICK) {
+        hz::set_error("hz_het_state: the STICKS chain has no Slidebank, RMSbank or Latchbank state");
+        return HZ_E_INVALID;
+    }
     HZ_TRY(het_flush(h));
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     const long N = h->N, Np = h->Np;
@@ -603,7 +1004,7 @@ int hz_het_state(hz_het* h, int what, double* dst) {
             dst[2 * i + 1] = im[i];
         }
     } else if (what == HZ_HET_STATE_SLIDE || what == HZ_HET_STATE_STICK) {
-        const int K = what == HZ_HET_STATE_SLIDE ? h->order : h->sorder;
+        const int K = what == HZ_HET_STATE_SLIDE ? h->order : sticks ? h->pre + h->post : h->sorder;
         const int f0 = what == HZ_HET_STATE_SLIDE ? F_SLIDE : F_STICK;
         for (int q = 0; q < K; ++q) {
             HZ_TRY(field(f0 + 2 * q, re));

@@ -9,6 +9,13 @@ limiter: process(x) returns, per sample,
             slidebank(modulators(x, analysis())))))))
 followed by the five ticks.  harmbank() builds the reference's instrument configuration
 (transpose() and measure() of tests/harmbank.cpp:108-200).
+
+Heterodyne(..., chain="phase") is the phase vocoder of tests/phasebank.cpp:77-101 (the latched
+signal split into absbank and argbank -> smoothbank, recombined by phase_combiners), phasebank()
+its configuration.  StickChain(channels, pre, post, rad, gate) is tests/oscbank.cpp:106-110:
+modulate, `pre` cascaded Stickbank(1, rad), Distbank(&gate), `post` more, demodulate, mix.
+set_output(shaper, drive, clip_width) selects the tail: tests/slidebank.cpp:95 is
+set_output(OUT_LIMITER, 4, 0.9) on a "harm" chain.
 """
 from __future__ import annotations
 
@@ -22,6 +29,8 @@ from ._lib import check, dptr, load
 SR = 48000
 ANALYSIS, SYNTHESIS = 0, 1
 STATE_ANALYSIS, STATE_SYNTHESIS, STATE_SLIDE, STATE_RMS, STATE_LATCH, STATE_STICK, STATE_HISTORY = range(7)
+CHAIN_HARM, CHAIN_PHASE, CHAIN_STICKS = range(3)
+OUT_LIMITER, OUT_RAW = 0, 1
 
 
 def mtof(m):   # src/includes.h: 440 * 2^((m - 69) / 12)
@@ -61,16 +70,25 @@ def harmbank(octaves=4, division=12, courses=1, harmonics=1, parities=2, detune=
     return n, fa, fs, radii
 
 
+def phasebank():
+    """The tests/phasebank.cpp instrument (phasebank.cpp:110-150,190-206): two octaves from
+    mtof(28), multiplicity 1, cutoff 0.999, synthesis an octave up and reversed."""
+    return harmbank(octaves=2, c1=28, multiplicity=1, cutoff=0.999)
+
+
 class Heterodyne:
     def __init__(self, channels, order, radii, thresh=0.0005, ratio=0.2, width=SR // 20, stick_order=1,
-                 stick_rad=-0.9, dry=0.0, gain=3.0, device=0):
+                 stick_rad=-0.9, dry=0.0, gain=3.0, device=0, chain="harm"):
         lib = load()
         radii = np.ascontiguousarray(radii, dtype=np.float64)
         if radii.size != 2 * channels:
             raise ValueError("radii: 2 x channels doubles (re, im)")
+        if chain not in ("harm", "phase"):
+            raise ValueError('chain: "harm" or "phase"')
+        create = lib.hz_het_create if chain == "harm" else lib.hz_het_create_phase
         h = C.c_void_p()
-        check(lib.hz_het_create(channels, order, dptr(radii), thresh, ratio, width, stick_order, stick_rad, dry,
-                                gain, device, C.byref(h)))
+        check(create(channels, order, dptr(radii), thresh, ratio, width, stick_order, stick_rad, dry, gain, device,
+                     C.byref(h)))
         self._h, self._lib = h, lib
         self.channels, self.order, self.width = channels, max(1, order), width
         self.stick_order = max(1, stick_order)
@@ -120,6 +138,14 @@ class Heterodyne:
         check(self._lib.hz_het_state(self._h, what, dptr(out)))
         return out
 
+    def chain(self):
+        c = C.c_int()
+        check(self._lib.hz_het_chain(self._h, C.byref(c)))
+        return c.value
+
+    def set_output(self, shaper=OUT_LIMITER, drive=0.0, clip_width=0.0):
+        check(self._lib.hz_het_set_output(self._h, shaper, drive, clip_width))
+
     def set_stream(self, stream):
         check(self._lib.hz_het_set_stream(self._h, C.c_void_p(stream)))
 
@@ -133,3 +159,16 @@ class Heterodyne:
         ms, launches, cs = C.c_double(), C.c_long(), C.c_long()
         check(self._lib.hz_het_profile_read(self._h, C.byref(ms), C.byref(launches), C.byref(cs)))
         return ms.value, launches.value, cs.value
+
+
+class StickChain(Heterodyne):
+    """tests/oscbank.cpp:106-110: dry x + gain mixdown(modbank2(oscbank2(), stickbank4(distbank(
+    stickbank3(stickbank2(stickbank(modbank1(x, oscbank1())))))))) with `pre` Stickbank(1, rad)
+    before Distbank(&gate) and `post` after it (gate <= 0: no Distbank)."""
+
+    def __init__(self, channels, pre=3, post=1, rad=-0.999, gate=0.001, dry=0.0, gain=1.0, device=0):
+        lib = load()
+        h = C.c_void_p()
+        check(lib.hz_het_create_sticks(channels, pre, post, rad, gate, dry, gain, device, C.byref(h)))
+        self._h, self._lib = h, lib
+        self.channels, self.order, self.width, self.stick_order = channels, 1, 0, pre + post

@@ -672,6 +672,33 @@ int hz_fb_process_tv_device(hz_fb* h, const double* d_in, double* d_out, size_t 
 typedef struct hz_het hz_het;
 int hz_het_create(int channels, int order, const double* radii, double thresh, double ratio, unsigned width,
                   int stick_order, double stick_rad, double dry, double gain, int device, hz_het** out);
+/* The other programs built from the same banks.  Every hz_het_* call below works on all three
+ * kinds of handle.
+ *   PHASE  tests/phasebank.cpp:77-101, the phase vocoder: the latched signal splits into
+ *          absbank (Distbank(&length)) and argbank (Distbank(&angle)) -> smoothbank, recombined
+ *          by phase_combiners before demodulators.  The Latchbank is called twice per sample
+ *          (magnitude path first, clang's argument order); the second call's RMSbank returns
+ *          sqrt(rms / width) (src/rmsbank.h:56-65).  HZ_HET_STATE_STICK is the phase path's
+ *          smoothbank, HZ_HET_STATE_LATCH the state after the second update.
+ *   STICKS tests/oscbank.cpp:106-110: modbank1, `pre` cascaded Stickbank(1, rad), Distbank(&gate)
+ *          (gate <= 0: none), `post` more, modbank2, Mixer; out = dry x + gain mix, no limiter
+ *          (HZ_HET_OUT_RAW).  1 <= pre + post <= 4.  HZ_HET_STATE_STICK is [channels][pre + post][2];
+ *          the Slidebank, RMS, latch and history selectors return HZ_E_INVALID and hz_het_setup
+ *          HZ_E_UNSUPPORTED.  The program's scalar tail (Buffer under an LFO) stays with the caller. */
+#define HZ_HET_CHAIN_HARM 0
+#define HZ_HET_CHAIN_PHASE 1
+#define HZ_HET_CHAIN_STICKS 2
+int hz_het_create_phase(int channels, int order, const double* radii, double thresh, double ratio, unsigned width,
+                        int stick_order, double stick_rad, double dry, double gain, int device, hz_het** out);
+int hz_het_create_sticks(int channels, int pre, int post, double rad, double gate, double dry, double gain,
+                         int device, hz_het** out);
+int hz_het_chain(hz_het* h, int* chain);
+/* Output stage: out = shaper(dry x + gain v), v = mix, or softclip(drive mix, clip_width) when
+ * drive != 0 (tests/slidebank.cpp:81-95: LIMITER, drive 4, clip_width 0.9; softclip is
+ * HZ_DIST_SOFTCLIP's).  Default: LIMITER, drive 0 (RAW for a STICKS handle). */
+#define HZ_HET_OUT_LIMITER 0
+#define HZ_HET_OUT_RAW 1
+int hz_het_set_output(hz_het* h, int shaper, double drive, double clip_width);
 int hz_het_destroy(hz_het* h);
 int hz_het_setup(hz_het* h, int order, const double* radii);                     /* slidebank.h:63-100 */
 int hz_het_freqmod(hz_het* h, int bank, const int* index, const double* hz, int count);   /* oscbank.h:49-56 */

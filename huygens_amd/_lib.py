@@ -222,6 +222,9 @@ _SIGS = {
     "hz_dly_profile_read": (I, [VP, PD, C.POINTER(L)]),
     "hz_stft_create": (I, [I, I, I, I, D, D, I, C.POINTER(VP)]),
     "hz_stft_create_long": (I, [I, I, I, I, D, D, I, C.POINTER(VP)]),
+    "hz_stft_set_params": (I, [VP, D, D]),
+    "hz_stft_transpose_sources": (I, [I, D, I, C.POINTER(I), C.POINTER(I)]),
+    "hz_stft_transpose_sources_range": (I, [I, D, I, I, C.POINTER(I), C.POINTER(I)]),
     "hz_stft_destroy": (I, [VP]),
     "hz_stft_set_processor": (I, [VP, VP]),
     "hz_stft_process_block": (I, [VP, PD, PD, PD, PD, SZ]),

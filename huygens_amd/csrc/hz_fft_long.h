@@ -39,6 +39,7 @@
 
 #include "hz_common.h"
 #include "hz_fft.h"
+#include "hz_transpose.h"
 
 namespace hzl {
 
@@ -299,7 +300,8 @@ __device__ __forceinline__ void wg_sum_dd(double& hi, double& lo, double* scratc
 // kRowFwdGate  workspace -> DIF -> spectrum back in place + this workgroup's partial magnitude sum
 // kRowGateInv  the frame's partials in index order -> threshold -> gate -> DIT -> x conj W -> workspace
 // kRowFwdOut   workspace -> DIF -> cdst in FFTW order (DCT: the REDFT10 rotation -> rdst)
-// kRowInInv    csrc in FFTW order (DCT: the REDFT01 rotation of rsrc) -> DIT -> x conj W -> workspace
+// kRowInInv    csrc in FFTW order (DCT: the REDFT01 rotation of rsrc) -> DIT -> x conj W -> workspace;
+//              PROC = HZ_PROC_TRANSPOSE: each bin gathered from csrc as the sum of its source run
 template <int PROC, int MODE, bool DCT>
 __global__ __launch_bounds__(kRowThreads) void long_row_kernel(Args a) {
 #pragma clang fp contract(off)
@@ -352,6 +354,19 @@ __global__ __launch_bounds__(kRowThreads) void long_row_kernel(Args a) {
                 const double2 w = a.rot[k];
                 vr = x0 * w.x + x1 * (-w.y);
                 vi = -x0 * w.y - x1 * w.x;
+            } else if constexpr (PROC == HZ_PROC_TRANSPOSE) {
+                // tests/demo.cpp:49-81 (p0 the ratio) as a gather from the spectrum in csrc: bin k
+                // adds its run of source bins in ascending order from +0.0 (hz_transpose.h)
+                int first, count;
+                hz::transpose_run((int)N, a.p0, (int)k, &first, &count);
+                const double2* sp = a.csrc + fl * N;
+                vr = 0.0;
+                vi = 0.0;
+                for (int s = first; s < first + count; ++s) {
+                    const double2 v = sp[s];
+                    vr += v.x;
+                    vi += v.y;
+                }
             } else {
                 const double2 v = a.csrc[fl * N + k];
                 vr = v.x;

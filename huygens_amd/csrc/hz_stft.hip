@@ -16,8 +16,8 @@
 //      order, in double-double (the reference accumulates in long double), and divides by
 //      the int N*laps/2.
 // Processors: identity, the StaticSTFT gate (staticSTFT.h:99-128), the spectral.cpp 625
-// gate (tests/spectral.cpp:32-72), the Hilbert half-band (tests/SFML/hilbert.cpp:37-49) as
-// device code; any other host function pointer runs per frame, in frame order, on the host
+// gate (tests/spectral.cpp:32-72), the Hilbert half-band (tests/SFML/hilbert.cpp:37-49) and the
+// pitch transposer (tests/demo.cpp:49-81, hz_transpose.h) as device code; any other host function pointer runs per frame, in frame order, on the host
 // between a forward-only and an inverse-only kernel, with each slot's `out` buffer kept
 // between frames as in the reference (fourier.h:57-59).
 //
@@ -38,6 +38,7 @@
 #include "hz_common.h"
 #include "hz_fft.h"
 #include "hz_fft_long.h"
+#include "hz_transpose.h"
 
 // Experiment builds only (-DHZ_STFT_ABLATE=mask; wrong results): 1 skip the processor,
 // 2 skip the inverse FFT, 4 skip the forward FFT, 8 skip the ring store, 16 twiddles = tw[0].
@@ -206,6 +207,65 @@ __device__ __forceinline__ void frame_middle(double* re, double* im, int lg, dou
     }
 }
 
+// The transposer's middle (HZ_PROC_TRANSPOSE, tests/demo.cpp:49-81) is not fused: an output bin
+// takes its sources from anywhere in the lower half of the spectrum.  The last forward pass goes
+// back to LDS (slot e holds bin bitrev(e)); after a barrier every thread gathers the bins of its
+// own group into registers -- bin k = bitrev(e0 + j) adds the run of hz::transpose_run in
+// ascending source bin, from +0.0 -- and after a second barrier (every read of the spectrum done)
+// runs the first inverse pass on them as frame_middle does.  No second frame in LDS.
+template <int R>
+__device__ __forceinline__ void frame_middle_transpose(double* re, double* im, int lg, double ratio, const double2* T) {
+    constexpr int M = 1 << R;
+    const int b = threadIdx.x, e0 = b << R, N = 1 << lg;
+    const bool act = b < (1 << (lg - R));
+    double xr[M], xi[M];
+    if (act) {
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+            xr[j] = re[hz::pad16(e0 + j)];
+            xi[j] = im[hz::pad16(e0 + j)];
+        }
+        hz::dif_regs<R, false>(xr, xi, lg, R - 1, 0, T);
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+            re[hz::pad16(e0 + j)] = xr[j];
+            im[hz::pad16(e0 + j)] = xi[j];
+        }
+    }
+    __syncthreads();
+    if (act) {
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+            int first, count;
+            hz::transpose_run(N, ratio, hz::bitrev(e0 + j, lg), &first, &count);
+            double sr = 0.0, si = 0.0;
+            for (int i = first; i < first + count; ++i) {
+                const int e = hz::pad16(hz::bitrev(i, lg));
+                sr += re[e];
+                si += im[e];
+            }
+            xr[j] = sr;
+            xi[j] = si;
+        }
+    }
+    __syncthreads();
+    if (act) {
+        hz::dit_regs<R, false>(xr, xi, lg, 0, 0, T);
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+            re[hz::pad16(e0 + j)] = xr[j];
+            im[hz::pad16(e0 + j)] = xi[j];
+        }
+    }
+}
+
+template <int R, int PROC>
+__device__ __forceinline__ void frame_middle_of(double* re, double* im, int lg, double p0, double p1, double* scratch,
+                                                const double2* T) {
+    if constexpr (PROC == HZ_PROC_TRANSPOSE) frame_middle_transpose<R>(re, im, lg, p0, T);
+    else frame_middle<R, PROC>(re, im, lg, p0, p1, scratch, T);
+}
+
 // stages per LDS pass: radix 8 up to N = 4096 (512 threads, 8 waves per frame), radix 16 above
 #ifndef HZ_STFT_R4_ABOVE
 #define HZ_STFT_R4_ABOVE 4096
@@ -303,9 +363,9 @@ __global__ __launch_bounds__(kFrameThreads) void stft_frame_kernel(StftArgs a) {
     } else {
         if constexpr (!(HZ_STFT_ABLATE & 4)) hz::fft_fwd_lead<RMAX>(re, im, lg, T, false);
         switch (hz::fft_rlast<RMAX>(lg)) {
-        case 4: if constexpr (RMAX >= 4) frame_middle<4, PROC>(re, im, lg, a.p0, a.p1, scratch, T); break;
-        case 3: frame_middle<3, PROC>(re, im, lg, a.p0, a.p1, scratch, T); break;
-        default: frame_middle<2, PROC>(re, im, lg, a.p0, a.p1, scratch, T); break;   // N = 4
+        case 4: if constexpr (RMAX >= 4) frame_middle_of<4, PROC>(re, im, lg, a.p0, a.p1, scratch, T); break;
+        case 3: frame_middle_of<3, PROC>(re, im, lg, a.p0, a.p1, scratch, T); break;
+        default: frame_middle_of<2, PROC>(re, im, lg, a.p0, a.p1, scratch, T); break;   // N = 4
         }
         __syncthreads();
         if constexpr (!(HZ_STFT_ABLATE & 2)) hz::fft_inv_tail<RMAX>(re, im, lg, T, false);
@@ -1138,6 +1198,17 @@ __global__ __launch_bounds__(kFrameThreads) void slot_proc_kernel(const double2*
         }
     } else if constexpr (PROC == HZ_PROC_HILBERT) {   // tests/SFML/hilbert.cpp:37-49: bins k < N/2
         for (int k = threadIdx.x; k < N; k += blockDim.x) out[k] = k < N / 2 ? in[k] : make_double2(0.0, 0.0);
+    } else if constexpr (PROC == HZ_PROC_TRANSPOSE) {   // tests/demo.cpp:49-81, p0 the ratio: gather form
+        for (int k = threadIdx.x; k < N; k += blockDim.x) {
+            int first, count;
+            hz::transpose_run(N, p0, k, &first, &count);
+            double sr = 0.0, si = 0.0;
+            for (int i = first; i < first + count; ++i) {
+                sr += in[i].x;
+                si += in[i].y;
+            }
+            out[k] = make_double2(sr, si);
+        }
     } else {
         for (int k = threadIdx.x; k < N; k += blockDim.x) out[k] = in[k];
     }
@@ -1161,6 +1232,9 @@ struct hz_stft {
     hz::Stream stream;
     int N = 0, laps = 0, stride = 0, lg = 0, window = 0, proc = 0, device = 0, R = 0;
     double p0 = 0, p1 = 0;
+    // hz_stft_set_params: held here until the next block call or slot process begins
+    bool staged = false;
+    double staged_p0 = 0, staged_p1 = 0;
     hz_stft_proc host_proc = nullptr;
     long T = 0;        // samples processed
     long frames = 0;   // frames completed
@@ -1203,6 +1277,22 @@ namespace {
 
 int stft_check(hz_stft* h) {
     return hz::check_handle(h, "hz_stft");
+}
+
+// the parameters a processor accepts, at creation and in hz_stft_set_params
+bool params_ok(const char* who, int proc, double p0) {
+    if (proc == HZ_PROC_TRANSPOSE && !hz::transpose_ratio_ok(p0)) {
+        hz::set_error("%s: the transposer's ratio must be finite and in [0, %g]", who, hz::kTransposeMaxRatio);
+        return false;
+    }
+    return true;
+}
+
+void apply_staged(hz_stft* h) {
+    if (!h->staged) return;
+    h->p0 = h->staged_p0;
+    h->p1 = h->staged_p1;
+    h->staged = false;
 }
 
 // number of frames with completion time e_f = s_f + N - 1 < T
@@ -1315,6 +1405,12 @@ int long_frames(hz_stft* h, const StftArgs& a, long nf, int mode) {
     } else if (h->proc == HZ_PROC_GATE_KEEP) {
         hzl::row<HZ_PROC_GATE_KEEP, hzl::kRowFwdGate, false>(l, nf, s);
         hzl::row<HZ_PROC_GATE_KEEP, hzl::kRowGateInv, false>(l, nf, s);
+    } else if (h->proc == HZ_PROC_TRANSPOSE) {
+        // a frame's bins span N1 / 4 row workgroups that work on ws in place, so the gather reads
+        // the spectrum from d_spec (a.spec, FFTW order); the sequence rewrites ws and d_spec from
+        // the input each time, so it may be repeated (hz_stft_profile)
+        hzl::row<HZ_PROC_IDENTITY, hzl::kRowFwdOut, false>(l, nf, s);
+        hzl::row<HZ_PROC_TRANSPOSE, hzl::kRowInInv, false>(l, nf, s);
     } else if (h->proc == HZ_PROC_HILBERT)
         hzl::row<HZ_PROC_HILBERT, hzl::kRowFused, false>(l, nf, s);
     else
@@ -1336,6 +1432,7 @@ int frames_fused(hz_stft* h, const StftArgs& a, long nf) {
     case HZ_PROC_STATIC_GATE: launch_frames<HZ_PROC_STATIC_GATE, 0>(h, a, nf); break;
     case HZ_PROC_GATE_KEEP: launch_frames<HZ_PROC_GATE_KEEP, 0>(h, a, nf); break;
     case HZ_PROC_HILBERT: launch_frames<HZ_PROC_HILBERT, 0>(h, a, nf); break;
+    case HZ_PROC_TRANSPOSE: launch_frames<HZ_PROC_TRANSPOSE, 0>(h, a, nf); break;
     default: launch_frames<HZ_PROC_IDENTITY, 0>(h, a, nf); break;
     }
     HZ_TRY_HIP(hipGetLastError());
@@ -1408,6 +1505,10 @@ int stft_block(hz_stft* h, const double* d_re, const double* d_im, double* d_ore
                     HZ_TRY_HIP(hipMemsetAsync(h->d_fo + (size_t)h->R * N + (size_t)(f % h->R) * N, 0,
                                               sizeof(double) * N, h->stream));
                 h->im_zero_from = LONG_MAX;
+            }
+            if (h->proc == HZ_PROC_TRANSPOSE && N > kMaxN) {   // the gather's spectrum buffer (long_frames)
+                HZ_TRY(h->d_spec.reserve((size_t)nf * N));
+                a.spec = h->d_spec;
             }
             if (h->proc != HZ_PROC_HOST) {
                 // profiling may repeat the (idempotent) frame launch so the event pair brackets
@@ -1510,10 +1611,11 @@ namespace {
 int stft_create(const char* who, int max_n, int N, int laps, int window, int proc, double p0, double p1, int device,
                 hz_stft** out) {
     if (!out || !pow2(N) || N > max_n || laps <= 0 || laps > N || (window != HZ_WIN_HALFHANN && window != HZ_WIN_HANN) ||
-        proc < HZ_PROC_IDENTITY || proc > HZ_PROC_HOST) {
+        proc < HZ_PROC_IDENTITY || proc > HZ_PROC_TRANSPOSE) {
         hz::set_error("%s: invalid arguments (N must be a power of two in [4, %d])", who, max_n);
         return HZ_E_INVALID;
     }
+    if (!params_ok(who, proc, p0)) return HZ_E_INVALID;
     *out = nullptr;
     HZ_TRY(hz::select_device(device));
     hz_stft* h = new (std::nothrow) hz_stft();
@@ -1594,6 +1696,7 @@ int stft_create(const char* who, int max_n, int N, int laps, int window, int pro
         frame_attr<HZ_PROC_STATIC_GATE, 0>(lds);
         frame_attr<HZ_PROC_GATE_KEEP, 0>(lds);
         frame_attr<HZ_PROC_HILBERT, 0>(lds);
+        frame_attr<HZ_PROC_TRANSPOSE, 0>(lds);
         frame_attr<HZ_PROC_IDENTITY, 1>(lds);
         frame_attr<HZ_PROC_IDENTITY, 2>(lds);
         for (const void* k : {(const void*)slot_fft_kernel<3, false>, (const void*)slot_fft_kernel<3, true>,
@@ -1638,6 +1741,40 @@ int hz_stft_set_processor(hz_stft* h, hz_stft_proc fn) {
     return HZ_OK;
 }
 
+int hz_stft_set_params(hz_stft* h, double p0, double p1) {
+    if (!h) {
+        hz::set_error("hz_stft_set_params: null handle");
+        return HZ_E_INVALID;
+    }
+    if (h->proc != HZ_PROC_STATIC_GATE && h->proc != HZ_PROC_GATE_KEEP && h->proc != HZ_PROC_TRANSPOSE) {
+        hz::set_error("hz_stft_set_params: processor %d has no parameters", h->proc);
+        return HZ_E_INVALID;
+    }
+    if (!params_ok("hz_stft_set_params", h->proc, p0)) return HZ_E_INVALID;
+    h->staged_p0 = p0;
+    h->staged_p1 = p1;
+    h->staged = true;
+    return HZ_OK;
+}
+
+int hz_stft_transpose_sources(int N, double ratio, int k, int* first, int* count) {
+    if (!first || !count || !pow2(N) || N > kMaxLongN || k < 0 || k >= N || !hz::transpose_ratio_ok(ratio)) {
+        hz::set_error("hz_stft_transpose_sources: invalid arguments");
+        return HZ_E_INVALID;
+    }
+    hz::transpose_run(N, ratio, k, first, count);
+    return HZ_OK;
+}
+
+int hz_stft_transpose_sources_range(int N, double ratio, int k0, int n, int* first, int* count) {
+    if (!first || !count || !pow2(N) || N > kMaxLongN || k0 < 0 || n < 0 || k0 > N - n || !hz::transpose_ratio_ok(ratio)) {
+        hz::set_error("hz_stft_transpose_sources_range: invalid arguments");
+        return HZ_E_INVALID;
+    }
+    for (int j = 0; j < n; ++j) hz::transpose_run(N, ratio, k0 + j, first + j, count + j);
+    return HZ_OK;
+}
+
 int hz_stft_process_block_device(hz_stft* h, const double* d_re, const double* d_im, double* d_out_re,
                                  double* d_out_im, size_t n) {
     HZ_TRY(stft_check(h));
@@ -1652,6 +1789,7 @@ int hz_stft_process_block_device(hz_stft* h, const double* d_re, const double* d
         hz::set_error("hz_stft: HZ_PROC_HOST without hz_stft_set_processor");
         return HZ_E_INVALID;
     }
+    apply_staged(h);   // hz_stft_set_params: from this call's first frame on
     return stft_run(h, d_re, d_im, d_out_re, d_out_im, (long)n);
 }
 
@@ -1751,6 +1889,7 @@ int slot_process(hz_stft* h, int i) {
     const int N = h->N;
     double2* mid = &h->s_mid[(size_t)i * N];
     double2* out = &h->s_out[(size_t)i * N];
+    apply_staged(h);   // hz_stft_set_params: from this slot on
     if (h->proc == HZ_PROC_HOST) {
         if (!h->host_proc) {
             hz::set_error("hz_stft: HZ_PROC_HOST without hz_stft_set_processor");
@@ -1774,6 +1913,10 @@ int slot_process(hz_stft* h, int i) {
         break;
     case HZ_PROC_HILBERT:
         hipLaunchKernelGGL(slot_proc_kernel<HZ_PROC_HILBERT>, dim3(1), dim3(kFrameThreads), 0, h->stream, a, b, N,
+                           h->p0, h->p1);
+        break;
+    case HZ_PROC_TRANSPOSE:
+        hipLaunchKernelGGL(slot_proc_kernel<HZ_PROC_TRANSPOSE>, dim3(1), dim3(kFrameThreads), 0, h->stream, a, b, N,
                            h->p0, h->p1);
         break;
     default:

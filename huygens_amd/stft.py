@@ -7,7 +7,9 @@ Cosine(N)                     src/fourier.h:197-234 (REDFT10 forward, REDFT01 ba
 N is a power of two up to 8192; long_frames=True (hz_stft_create_long) allows up to 262144, and
 builds the same engine below the limit.  Cosine takes N up to 262144 as it is.  params=(p0, p1)
 replaces a built-in gate's constants: Fourier(PROC_GATE_KEEP, N, laps, params=(10.0, 0.0)) keeps
-the bins with |X|^2 > 10 average^2.
+the bins with |X|^2 > 10 average^2.  Fourier(PROC_TRANSPOSE, N, laps, params=(ratio, 0.0)) is the
+pitch transposer of tests/demo.cpp:49-81 on the device (ratio 2 by default, finite, in [0, 8192]);
+set_params(p0, p1) moves a gate's constants or the ratio between calls.
 
 process_block(re, im) == n x { write(re[t], im[t]); read(&re_out, &im_out); }.
 A processor is a built-in id (PROC_*) or a Python callable f(inp, out) over complex128
@@ -23,7 +25,8 @@ from ._lib import check, dptr, load
 
 WIN_HALFHANN, WIN_HANN = 0, 1
 PROC_IDENTITY, PROC_STATIC_GATE, PROC_GATE_KEEP, PROC_HILBERT, PROC_HOST = 0, 1, 2, 3, 4
-_PARAMS = {PROC_STATIC_GATE: (100.0, 0.1), PROC_GATE_KEEP: (625.0, 0.0)}
+PROC_TRANSPOSE = 5   # tests/demo.cpp:49-81, p0 = ratio
+_PARAMS = {PROC_STATIC_GATE: (100.0, 0.1), PROC_GATE_KEEP: (625.0, 0.0), PROC_TRANSPOSE: (2.0, 0.0)}
 PROC_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double))
 
 
@@ -98,6 +101,12 @@ class Fourier:
     def process(self, slot: int):
         check(self._lib.hz_stft_process_slot(self._h, int(slot)))
 
+    def set_params(self, p0: float, p1: float = 0.0):
+        """Stage new processor parameters (a gate's constants, the transposer's ratio): they take
+        effect with the first frame of the next process_block call, or per sample with the next
+        completed frame (hz_stft_set_params)."""
+        check(self._lib.hz_stft_set_params(self._h, float(p0), float(p1)))
+
     def set_frame_shard(self, rank: int, world: int, block: int):
         """Time-range shard: compute frame f iff (f // block) % world == rank
         (hz_stft_set_frame_shard); the ranks' outputs sum to the unsharded output."""
@@ -125,6 +134,22 @@ def frames_before(N: int, laps: int, samples: int) -> int:
     f = C.c_long()
     check(load().hz_stft_frames_before(N, laps, int(samples), C.byref(f)))
     return f.value
+
+
+def transpose_sources(N: int, ratio: float, k=None):
+    """The source bins [first, first + count) that PROC_TRANSPOSE adds into output bin k of an
+    N-point frame, from the function the kernels call (hz_stft_transpose_sources; no GPU needed).
+    k None: two int32 arrays (first, count) over every bin."""
+    lib = load()
+    if k is None:
+        first, count = np.empty(N, dtype=np.int32), np.empty(N, dtype=np.int32)
+        ip = C.POINTER(C.c_int)
+        check(lib.hz_stft_transpose_sources_range(N, float(ratio), 0, N, first.ctypes.data_as(ip),
+                                                  count.ctypes.data_as(ip)))
+        return first, count
+    a, b = C.c_int(), C.c_int()
+    check(lib.hz_stft_transpose_sources(N, float(ratio), int(k), C.byref(a), C.byref(b)))
+    return a.value, b.value
 
 
 class StaticSTFT(Fourier):

@@ -500,6 +500,7 @@ int hz_bowl_fill_delaybank(hz_bowl* bowl, float* d_buffer, hz_dly* bank, void* d
 #define HZ_PROC_GATE_KEEP 2   /* p0 = 625: tests/spectral.cpp:32-72 */
 #define HZ_PROC_HILBERT 3     /* tests/SFML/hilbert.cpp:37-49 */
 #define HZ_PROC_HOST 4        /* host function pointer, per frame, in frame order */
+#define HZ_PROC_TRANSPOSE 5   /* p0 = ratio: tests/demo.cpp:49-81 */
 /* the reference's processor type; complex<double>* passed as interleaved double* */
 typedef int (*hz_stft_proc)(const double* in, double* out);
 typedef struct hz_stft hz_stft;
@@ -510,6 +511,31 @@ int hz_stft_create(int N, int laps, int window, int proc, double p0, double p1, 
  * gate); every call of this section works on such a handle except time-range shards:
  * hz_stft_set_frame_shard with world > 1 returns HZ_E_UNSUPPORTED. */
 int hz_stft_create_long(int N, int laps, int window, int proc, double p0, double p1, int device, hz_stft** out);
+/* HZ_PROC_TRANSPOSE is the pitch transposer of tests/demo.cpp:49-81 as a device processor, with
+ * p0 the ratio (the program's `transp`; p1 is ignored):
+ *     out[*] = 0;  for i < N/2: ix = int(i * ratio), if (ix < N) out[ix] += in[i];
+ *     for i >= N/2: out[i] = out[N - i]
+ * computed as a gather: bin k <= N/2 is the sum of its contiguous run of source bins in ascending
+ * order from +0.0, bin k > N/2 that of bin N - k (a plain mirror, not a conjugate: the output of
+ * real input is complex, as in the reference).  The program's phase and amplitude bookkeeping
+ * never reaches `out` and is not built; no state is kept between frames.  The ratio must be finite
+ * and in [0, 8192] (int(i * ratio) is then defined for every i < 2^17); anything else is
+ * HZ_E_INVALID.  Above 8192 points the frame launches are column forward, row forward to a
+ * spectrum buffer, a row inverse that gathers from it, column inverse: four, as with a gate.
+ *
+ * hz_stft_set_params stages new (p0, p1) for a handle whose processor has parameters
+ * (HZ_PROC_STATIC_GATE, HZ_PROC_GATE_KEEP, HZ_PROC_TRANSPOSE; validated as at creation;
+ * HZ_E_INVALID for the identity, Hilbert and host processors).  They take effect with the first
+ * frame processed by the next hz_stft_process_block[_device] call, or per sample with the next
+ * hz_stft_process_slot / completed frame -- never inside a call.
+ *
+ * hz_stft_transpose_sources: the source run [*first, *first + *count) of output bin k of an
+ * N-point frame, 0 <= k < N (N a power of two in [4, 262144]), from the function the kernels
+ * call.  No device is needed.  hz_stft_transpose_sources_range fills first[j], count[j] for the n
+ * bins k0 + j (k0 + n <= N) with the same function. */
+int hz_stft_set_params(hz_stft* h, double p0, double p1);
+int hz_stft_transpose_sources(int N, double ratio, int k, int* first, int* count);
+int hz_stft_transpose_sources_range(int N, double ratio, int k0, int n, int* first, int* count);
 int hz_stft_destroy(hz_stft* h);
 int hz_stft_set_processor(hz_stft* h, hz_stft_proc fn);
 int hz_stft_process_block(hz_stft* h, const double* re, const double* im, double* out_re, double* out_im, size_t n);
@@ -545,7 +571,9 @@ int hz_stft_set_stream(hz_stft* h, void* hip_stream);
 int hz_stft_synchronize(hz_stft* h);
 /* Event timing of the frame and overlap-add kernels.  enable > 1 repeats each block's
  * (idempotent) device-processor frame launch `enable` times between the events, so the
- * event overhead is amortised; profile_read then reports frame_ms per single launch. */
+ * event overhead is amortised; profile_read then reports frame_ms per single launch.  The
+ * transposer's four launches above 8192 points rewrite their buffers from the input each time,
+ * so they repeat like the others. */
 int hz_stft_profile(hz_stft* h, int enable);
 /* (reading resets the counters) */
 int hz_stft_profile_read(hz_stft* h, double* frame_ms, double* ola_ms, long* blocks);

@@ -23,6 +23,13 @@ public:
     Fourier(processor_t processor, int N, int laps, int device = 0) { init(HZ_PROC_HOST, N, laps, HZ_WIN_HALFHANN, device, processor); }
     // built-in device processor: HZ_PROC_IDENTITY, HZ_PROC_GATE_KEEP (625), HZ_PROC_HILBERT
     Fourier(int builtin, int N, int laps, int device = 0) { init(builtin, N, laps, HZ_WIN_HALFHANN, device, nullptr); }
+    // a built-in with its parameters: Fourier(HZ_PROC_TRANSPOSE, N, laps, ratio, 0) is the processor of
+    // tests/demo.cpp:49-81 on the device; Fourier(HZ_PROC_GATE_KEEP, N, laps, 10, 0) the octave programs' gate
+    Fourier(int builtin, int N, int laps, double p0, double p1, int device = 0) {
+        create(builtin, N, laps, HZ_WIN_HALFHANN, device, nullptr, p0, p1);
+    }
+    // new (p0, p1) from the next completed frame (per sample) or the next process_block call on
+    void set_params(double p0, double p1 = 0) { detail::check(hz_stft_set_params(h_.get(), p0, p1), "Fourier::set_params"); }
 
     void write(double real, double imag = 0) { detail::check(hz_stft_write(h_.get(), real, imag), "Fourier::write"); }
     void read(double* real, double* imag) { detail::check(hz_stft_read(h_.get(), real, imag), "Fourier::read"); }
@@ -39,6 +46,9 @@ protected:
     void init(int proc, int N, int laps, int window, int device, processor_t fn) {
         const double p0 = proc == HZ_PROC_STATIC_GATE ? 100.0 : (proc == HZ_PROC_GATE_KEEP ? 625.0 : 0.0);
         const double p1 = proc == HZ_PROC_STATIC_GATE ? 0.1 : 0.0;
+        create(proc, N, laps, window, device, fn, proc == HZ_PROC_TRANSPOSE ? 2.0 : p0, p1);
+    }
+    void create(int proc, int N, int laps, int window, int device, processor_t fn, double p0, double p1) {
         hz_stft* h = nullptr;
         detail::check(hz_stft_create_long(N, laps, window, proc, p0, p1, device, &h), "Fourier");
         h_ = decltype(h_)(h);

@@ -35,15 +35,16 @@
 
 #include "hz_common.h"
 #include "hz_minimizer.h"
+#include "hz_mix.h"
+#include "hz_mixplan.h"
 
 namespace {
 
+using namespace hz::mix;   // kWaves, kMaxPerWave, kPad, cmul, lane_d and the end-of-tile / slab reductions
+
 constexpr int kL = 32;   // samples per lane chunk (16: 1.28 ms per C3 launch; 32 halves the per-chunk
                          // seed / table / transient-check work per sample)
-constexpr int kTile = 64 * kL;
-constexpr int kWaves = 8;
-constexpr int kMaxPerWave = 64;
-constexpr int kPad = 66;
+constexpr int kTile = tile_len(kL);
 
 // per-partial record (depends only on the target frequency and the output weight):
 // A = f_target/SR (cycles/sample), c (output weight), W1 = e^{2 pi i A},
@@ -83,21 +84,6 @@ struct AddArgs {
     double a;              // attack smoothing coefficient
     double s;              // oscillator stiffness
 };
-
-__device__ __forceinline__ void cmul(double ar, double ai, double br, double bi, double& cr, double& ci) {
-    const double r = fma(ar, br, -ai * bi);
-    const double i = fma(ar, bi, ai * br);
-    cr = r;
-    ci = i;
-}
-
-// lane q's double (q uniform)
-__device__ __forceinline__ double lane_d(double v, int q) {
-    const long long b = __builtin_bit_cast(long long, v);
-    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffff), q);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), q);
-    return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
-}
 
 // frac(phi0 + A t + D (1 - s^t)) with the A t product kept exact (fma residual)
 __device__ __forceinline__ double phase_at(double phi0, double A, double D, double s, double t, double st) {
@@ -235,35 +221,13 @@ __global__ __launch_bounds__(64 * kWaves) void add_mix_kernel(const double* __re
                 }
             }
         }
-        __syncthreads();
         const bool direct = gridDim.x == 1;   // one group: the output itself, scaled
-        for (int tl = threadIdx.x; tl < kTile; tl += blockDim.x) {
-            const int src = tl / kL, j = tl % kL;
-            double s0 = 0.0;
-#pragma unroll
-            for (int w = 0; w < kWaves; ++w) s0 += part[w * (kL * kPad) + j * kPad + src];
-            const long t = t0 + tl;
-            if (t < a.n) {
-                if (direct) a.partial[t] = s0 * a.scale;
-                else a.partial[(long)blockIdx.x * a.n_pad + t] = s0;
-            }
-        }
-        __syncthreads();
+        tile_reduce<kL, 1>(part, t0, a.n, [&](long t, const double (&s0)[1]) {
+            if (direct) a.partial[t] = s0[0] * a.scale;
+            else a.partial[(long)blockIdx.x * a.n_pad + t] = s0[0];
+        });
         a_t *= pow(a.a, (double)kTile);
     }
-}
-
-__global__ __launch_bounds__(256) void add_reduce_kernel(const double* __restrict__ partial, long n_pad, int G,
-                                                         long n, double scale, double* __restrict__ out) {
-    __shared__ double red[4][64];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const long t = (long)blockIdx.x * 64 + tx;
-    double s = 0.0;
-    if (t < n)
-        for (int g = ty; g < G; g += 4) s += partial[(long)g * n_pad + t];
-    red[ty][tx] = s;
-    __syncthreads();
-    if (ty == 0 && t < n) out[t] = ((red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx])) * scale;
 }
 
 // end-of-call oscillator state for the partials of alive voices:
@@ -443,22 +407,13 @@ struct PhaseBank {
             // cut the partial rows -- one group writes the output directly, 146 -> 67 MB counted per
             // C3 step -- but measured slower (C3: 19 groups 1.19 ms, 4: 1.46, 2: 1.86; one group for the
             // long call 1.47 ms: every workgroup then streams all 3.7 MB of partial records per tile)
-            const long ntiles = (n + kTile - 1) / kTile;
             // (tpw is fixed at 1 here; the kernel's loop over a wave's tasks stays as it is)
             const int G = (ntasks + kWaves - 1) / kWaves, tpw = 1;
-            long nseg = std::max<long>(1, std::min<long>(ntiles, (target_groups + G - 1) / G));
-            const long seg_tiles = (ntiles + nseg - 1) / nseg;
-            nseg = (ntiles + seg_tiles - 1) / seg_tiles;
-            const long n_pad = ntiles * kTile;
-            const size_t need = G > 1 ? (size_t)G * n_pad : 1;
+            const hz::MixPlan mp = hz::mix_plan(G, n, kTile, target_groups);
+            const size_t need = G > 1 ? (size_t)G * mp.n_pad : 1;
             HZ_TRY(d_partial.reserve(need));
-            const size_t lds = sizeof(double) * (kWaves * kL * kPad);
-            static bool attr = false;
-            if (!attr) {
-                HZ_TRY_HIP(hipFuncSetAttribute((const void*)add_mix_kernel,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                attr = true;
-            }
+            const size_t lds = sizeof(double) * plane_len(kL);
+            HZ_TRY(hz::allow_lds(device, (const void*)add_mix_kernel, lds));
             AddArgs args;
             args.tasks = d_tasks;
             args.phi = d_phi;
@@ -471,18 +426,17 @@ struct PhaseBank {
             args.scale = scale;
             args.tpw = tpw;
             args.n = n;
-            args.n_pad = n_pad;
-            args.seg_len = seg_tiles * kTile;
+            args.n_pad = mp.n_pad;
+            args.seg_len = mp.seg_len;
             args.ntasks = ntasks;
-            args.nseg = (int)nseg;
+            args.nseg = (int)mp.nseg;
             args.a = a;
             args.s = s;
-            hipLaunchKernelGGL(add_mix_kernel, dim3(G, (unsigned)nseg), dim3(64 * kWaves), lds, stream,
+            hipLaunchKernelGGL(add_mix_kernel, dim3(G, (unsigned)mp.nseg), dim3(64 * kWaves), lds, stream,
                                (const double*)d_rec, args);
             HZ_TRY_HIP(hipGetLastError());
             if (G > 1) {
-                hipLaunchKernelGGL(add_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, stream,
-                                   (const double*)d_partial, n_pad, G, n, scale, d_dst);
+                slab_reduce(stream, (const double*)d_partial, mp.n_pad, G, n, SlabScale{scale, d_dst});
                 HZ_TRY_HIP(hipGetLastError());
             }
             const double s_n = (double)powl((long double)s, (long double)n);
@@ -728,8 +682,7 @@ int phys_audio(hz_add* h, double* d_dst, long n, const double* rows, int period,
     a.s = b.s;
     a.advance = advance;
     HZ_TRY(hz::add_track(b.stream, a));
-    hipLaunchKernelGGL(add_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, b.stream,
-                       (const double*)ph.d_partial, n, G, n, b.scale, d_dst);
+    slab_reduce(b.stream, (const double*)ph.d_partial, n, G, n, SlabScale{b.scale, d_dst});
     HZ_TRY_HIP(hipGetLastError());
     return HZ_OK;
 }

@@ -30,14 +30,15 @@
 
 #include "hz_chain.h"
 #include "hz_common.h"
+#include "hz_mix.h"
+#include "hz_mixplan.h"
 
 namespace {
 
+using namespace hz::mix;   // kWaves, kMaxPerWave, kPad, cmul and the end-of-tile / slab reductions
+
 constexpr int kL = 16;
-constexpr int kTile = 64 * kL;
-constexpr int kWaves = 8;
-constexpr int kMaxPerWave = 64;
-constexpr int kPad = 66;
+constexpr int kTile = tile_len(kL);
 constexpr double kPiM = 3.141592653589793115997963468544185161590576171875;  // M_PI (double)
 
 // per-mode record: a, W1 (2), T1[16] (32), T2[4] (8), WT (2), f, d, |w|  (48 doubles)
@@ -59,13 +60,6 @@ struct BowlArgs {
     double n0;        // phase counter at call start
     int M, nseg, per_wave, is_float;
 };
-
-__device__ __forceinline__ void cmul(double ar, double ai, double br, double bi, double& cr, double& ci) {
-    const double r = fma(ar, br, -ai * bi);
-    const double i = fma(ar, bi, ai * br);
-    cr = r;
-    ci = i;
-}
 
 // x / 48000 correctly rounded (binary32) without the IEEE divide sequence: q = x * RN(1/SR),
 // then one FMA residual step (Markstein).  Checked exhaustively against x / 48000.0f over all
@@ -193,34 +187,11 @@ __global__ __launch_bounds__(64 * kWaves) void bowl_mix_kernel(const double* __r
                 }
             }
         }
-        double* my = part + wave * (kL * kPad);
-#pragma unroll
-        for (int j = 0; j < kL; ++j) my[j * kPad + lane] = acc[j];
-        __syncthreads();
-        for (int tl = threadIdx.x; tl < kTile; tl += blockDim.x) {
-            const int src = tl >> 4, j = tl & 15;
-            double s0 = 0.0;
-#pragma unroll
-            for (int w = 0; w < kWaves; ++w) s0 += part[w * (kL * kPad) + j * kPad + src];
-            const long t = t0 + tl;
-            if (t < a.n) a.partial[(long)blockIdx.x * a.n_pad + t] = s0;
-        }
-        __syncthreads();
+        put_rows<kL>(part + wave * (kL * kPad), lane, acc);
+        tile_reduce<kL, 1>(part, t0, a.n, [&](long t, const double (&s0)[1]) {
+            a.partial[(long)blockIdx.x * a.n_pad + t] = s0[0];
+        });
     }
-}
-
-template <typename OutT>
-__global__ __launch_bounds__(256) void bowl_reduce_kernel(const double* __restrict__ partial, long n_pad, int G,
-                                                          long n, OutT* __restrict__ out) {
-    __shared__ double red[4][64];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const long t = (long)blockIdx.x * 64 + tx;
-    double s = 0.0;
-    if (t < n)
-        for (int g = ty; g < G; g += 4) s += partial[(long)g * n_pad + t];
-    red[ty][tx] = s;
-    __syncthreads();
-    if (ty == 0 && t < n) out[t] = (OutT)((red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx]));
 }
 
 // short calls (a streamed 1024-sample block): 16 row slices per 64 samples, the loads of a
@@ -464,26 +435,18 @@ int bowl_check(hz_bowl* h) {
 int bowl_launch(hz_bowl* h, void* d_dst, long n, int out_kind) {
     if (n <= 0) return HZ_OK;
     const int M = h->M;
-    const long ntiles = (n + kTile - 1) / kTile;
+    const long ntiles = (n + kTile - 1) / kTile;   // (the clamp below needs it before the plan)
     // modes per wave: up to 64 when time segments alone fill the chip; fewer (down to one)
     // for short calls so that modes x segments still give ~2 workgroups per CU
     int per_wave = std::min(kMaxPerWave, std::max(1, (M + kWaves * 32 - 1) / (kWaves * 32)));
     const long par = (long)M * ntiles / ((long)kWaves * 2 * h->target_groups);
     if (par < per_wave) per_wave = (int)std::max<long>(1, par);
     const int G = std::max(1, (M + kWaves * per_wave - 1) / (kWaves * per_wave));
-    long nseg = std::max<long>(1, std::min<long>(ntiles, (h->target_groups + G - 1) / G));
-    const long seg_tiles = (ntiles + nseg - 1) / nseg;
-    nseg = (ntiles + seg_tiles - 1) / seg_tiles;
-    const long n_pad = ntiles * kTile;
-    const size_t need = (size_t)G * n_pad;
-    HZ_TRY(h->d_partial.reserve(need));
-    const size_t lds = sizeof(double) * (kWaves * kL * kPad + kWaves * 2 * kMaxPerWave);
-    static bool attr = false;
-    if (!attr) {
-        HZ_TRY_HIP(hipFuncSetAttribute((const void*)bowl_mix_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds));
-        attr = true;
-    }
+    const hz::MixPlan mp = hz::mix_plan(G, n, kTile, h->target_groups);
+    const long n_pad = mp.n_pad;
+    HZ_TRY(h->d_partial.reserve((size_t)G * n_pad));
+    const size_t lds = sizeof(double) * (plane_len(kL) + kWaves * 2 * kMaxPerWave);
+    HZ_TRY(hz::allow_lds(h->device, (const void*)bowl_mix_kernel, lds));
     hipEvent_t* e = nullptr;
     if (h->prof) {
         HZ_TRY(h->ev.take(2, &e));
@@ -493,13 +456,13 @@ int bowl_launch(hz_bowl* h, void* d_dst, long n, int out_kind) {
     args.partial = h->d_partial;
     args.n = n;
     args.n_pad = n_pad;
-    args.seg_len = seg_tiles * kTile;
+    args.seg_len = mp.seg_len;
     args.n0 = h->n0;
     args.M = M;
-    args.nseg = (int)nseg;
+    args.nseg = (int)mp.nseg;
     args.per_wave = per_wave;
     args.is_float = h->is_float;
-    hipLaunchKernelGGL(bowl_mix_kernel, dim3(G, (unsigned)nseg), dim3(64 * kWaves), lds, h->stream,
+    hipLaunchKernelGGL(bowl_mix_kernel, dim3(G, (unsigned)mp.nseg), dim3(64 * kWaves), lds, h->stream,
                        (const double*)h->d_rec, args);
     HZ_TRY_HIP(hipGetLastError());
     if (e) HZ_TRY_HIP(hipEventRecord(e[1], h->stream));
@@ -513,11 +476,9 @@ int bowl_launch(hz_bowl* h, void* d_dst, long n, int out_kind) {
                                dim3(64 * kShortSlices), 0, h->stream, (const double*)h->d_partial, n_pad, G, n,
                                (double*)d_dst);
     } else if (out_kind == 0)
-        hipLaunchKernelGGL(bowl_reduce_kernel<float>, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, h->stream,
-                           (const double*)h->d_partial, n_pad, G, n, (float*)d_dst);
+        slab_reduce(h->stream, (const double*)h->d_partial, n_pad, G, n, SlabStore<float>{(float*)d_dst});
     else
-        hipLaunchKernelGGL(bowl_reduce_kernel<double>, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, h->stream,
-                           (const double*)h->d_partial, n_pad, G, n, (double*)d_dst);
+        slab_reduce(h->stream, (const double*)h->d_partial, n_pad, G, n, SlabStore<double>{(double*)d_dst});
     HZ_TRY_HIP(hipGetLastError());
     // phase counter: T = double counts exactly; T = float saturates at 2^24
     h->n0 += (double)n;

@@ -8,6 +8,7 @@
 
 #include "../../include/huygens_hip.h"
 #include "hz_buf.h"
+#include "hz_lds.h"
 #include "hz_stream.h"
 
 namespace hz {

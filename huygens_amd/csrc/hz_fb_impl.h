@@ -18,12 +18,15 @@
 #include <vector>
 
 #include "hz_common.h"
+#include "hz_mix.h"
+#include "hz_mixplan.h"
 
 namespace hz_fbi {
 
 constexpr int kMaxOrder = 4;
 constexpr int kLtiGeomChunk128 = 3;   // hz_fb_lti.hip kLtiGeoms: chunk 128 (8192-sample tiles)
 constexpr int kStreamBlock = 1024;    // hz_fb_stream.hip: the streaming engine's call length
+constexpr size_t kLdsCeiling = 160 * 1024;   // the dynamic-LDS limit the mix kernels are granted (a CU's LDS)
 
 // MODE_MIX: full pass (mixdown) over one time segment (blockIdx.y) of one band group
 //   (blockIdx.x).
@@ -52,15 +55,8 @@ __device__ __forceinline__ double dpp_d(double v) {
     return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 constexpr int kDppRowShr = 0x110;   // row_shr:n = 0x110 + n (within 16-lane rows)
-// (wave-wide DPP shifts / row_bcast do not exist on CDNA; cross-row moves use
-//  ds_bpermute or v_readlane)
 
-__device__ __forceinline__ double readlane_d(double v, int l) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffff), l);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
+using hz::mix::lane_d;   // a lane's double by v_readlane
 
 }  // namespace hz_fbi
 
@@ -360,7 +356,6 @@ struct SampleLock {
 };
 
 // hz_filterbank.hip
-int fb_set_lds_attr(const void* kernel);
 int fb_prof_events(hz_fb* h, hipEvent_t** e);
 void fb_mirror_advance(hz_fb* h, long len);  // O(1): the closed form is applied lazily
 void fb_mirror_sync(hz_fb* h);               // bring pg_host up to date (before a setter)

@@ -683,7 +683,7 @@ __global__ __launch_bounds__(64 * lti_waves(O)) void fb_lti_kernel(const double*
                 double Sn[O];
 #pragma unroll
                 for (int k = 0; k < O; ++k) {
-                    double sn = readlane_d(v[k], 63);
+                    double sn = lane_d(v[k], 63);
 #pragma unroll
                     for (int c = 0; c < O; ++c) sn = fma(r[R::PSL + k * O + c], S[c], sn);
 #pragma unroll
@@ -724,7 +724,7 @@ __global__ __launch_bounds__(64 * lti_waves(O)) void fb_lti_kernel(const double*
 #pragma unroll
             for (int k = 0; k < O; ++k) {
                 double vv = dpp_dm<kDppWaveShr1, 0xf>(zz[k]);  // Z(l-1), 0 at lane 0
-                double sn = readlane_d(zz[k], 63);
+                double sn = lane_d(zz[k], 63);
 #pragma unroll
                 for (int c = 0; c < O; ++c) sn = fma(r[R::PSL + k * O + c], S[c], sn);
 #pragma unroll
@@ -1350,8 +1350,7 @@ int fb_launch_lti(hz_fb* h, int gi, const double* d_in, double* d_out, long n) {
     const hz::Event* ev_red = h->sync_ev.data() + nchunks;
     LtiKernel kmix = pick_lti(O, gi, gemm ? MODE_STATE : MODE_MIX);
     LtiKernel kend = pick_lti(O, gi, MODE_SEGEND);
-    HZ_TRY(fb_set_lds_attr((const void*)kmix));
-    HZ_TRY(fb_set_lds_attr((const void*)kend));
+    HZ_TRY(hz::allow_lds(h->device, {(const void*)kmix, (const void*)kend}, kLdsCeiling));
     const size_t lds = lti_lds(O, gi, !gemm);
     const size_t lds_end = lti_lds(O, gi, false);
     // with the reduce on a second stream, the first chunk's reduce reads the call's x history
@@ -1365,10 +1364,9 @@ int fb_launch_lti(hz_fb* h, int gi, const double* d_in, double* d_out, long n) {
     long k = 0;
     for (long off = 0; off < n; off += chunk, ++k) {
         const long len = std::min(chunk, n - off);
-        const long ntiles = (len + T - 1) / T;
-        long nseg = std::max<long>(1, std::min<long>(ntiles, (h->target_groups + G - 1) / G));
-        long seg_tiles = (ntiles + nseg - 1) / nseg;
-        nseg = (ntiles + seg_tiles - 1) / seg_tiles;
+        const hz::MixPlan mp = hz::mix_plan(G, len, (int)T, h->target_groups);
+        const long ntiles = mp.ntiles;
+        long nseg = mp.nseg, seg_tiles = mp.seg_tiles;
         // The prepass (zero-start end states of segments 0 .. nseg-2) runs on G (nseg - 1)
         // workgroups, a fraction of the chip when few segments are needed (2 GPUs: 128 of 256
         // CUs).  Split each prepass segment in m equal parts, m minimising the prepass rounds

@@ -602,26 +602,25 @@ int macc_splits(int Qp) { return std::min(2, Qp / kMacChunk); }
 // the LDS-staged MAC: Qp = 8, 16, 24 or whole chunks of 24 (q_padded) (C2: 6.1 against 7.4 us per
 // launch of the register-only kernel, step 29.4 against 30.6 us, alternating runs on one box,
 // profiles/r5/mac/summary.txt)
-void launch_mac_lds(int Qp, int B, const double2* H, const double2* Z, double2* Y, int Q, hipStream_t s) {
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)resp_mac_kernel_lds<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mac_lds_bytes<8>());
-        (void)hipFuncSetAttribute((const void*)resp_mac_kernel_lds<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mac_lds_bytes<16>());
-        (void)hipFuncSetAttribute((const void*)resp_mac_kernel_lds<24>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mac_lds_bytes<24>());
-        (void)hipFuncSetAttribute((const void*)resp_mac_kernel_ldsc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaccLdsBytes);
-        attr = true;
-    }
+template <int QP>
+int launch_mac_lds_qp(int device, dim3 grid, int B, const double2* H, const double2* Z, double2* Y, int Q, hipStream_t s) {
+    HZ_TRY(hz::allow_lds(device, (const void*)resp_mac_kernel_lds<QP>, mac_lds_bytes<QP>()));
+    hipLaunchKernelGGL(resp_mac_kernel_lds<QP>, grid, dim3(256), (mac_lds_bytes<QP>()), s, H, Z, Y, Q, B);
+    return HZ_OK;
+}
+int launch_mac_lds(int device, int Qp, int B, const double2* H, const double2* Z, double2* Y, int Q, hipStream_t s) {
     if (Qp > kMacChunk) {   // long horizons: partitions in chunks of 24
         constexpr int blk = (256 / kMaccBins) * kMacBpw;
         const int ns = macc_splits(Qp), nch = Qp / kMacChunk, cps = (nch + ns - 1) / ns;
         const dim3 grid((unsigned)((kH / kMaccBins) * ((B + blk - 1) / blk)), (unsigned)ns);
+        HZ_TRY(hz::allow_lds(device, (const void*)resp_mac_kernel_ldsc, kMaccLdsBytes));
         hipLaunchKernelGGL(resp_mac_kernel_ldsc, grid, dim3(256), kMaccLdsBytes, s, H, Z, Y, Q, B, nch, cps, (long)B * kH);
-        return;
+        return HZ_OK;
     }
     const dim3 grid((unsigned)((kH / kMacBins) * ((B + 4 * kMacBpw - 1) / (4 * kMacBpw))));
-    if (Qp == 8) hipLaunchKernelGGL(resp_mac_kernel_lds<8>, grid, dim3(256), (mac_lds_bytes<8>()), s, H, Z, Y, Q, B);
-    else if (Qp == 16) hipLaunchKernelGGL(resp_mac_kernel_lds<16>, grid, dim3(256), (mac_lds_bytes<16>()), s, H, Z, Y, Q, B);
-    else hipLaunchKernelGGL(resp_mac_kernel_lds<24>, grid, dim3(256), (mac_lds_bytes<24>()), s, H, Z, Y, Q, B);
+    if (Qp == 8) return launch_mac_lds_qp<8>(device, grid, B, H, Z, Y, Q, s);
+    if (Qp == 16) return launch_mac_lds_qp<16>(device, grid, B, H, Z, Y, Q, s);
+    return launch_mac_lds_qp<24>(device, grid, B, H, Z, Y, Q, s);
 }
 
 // the register-only MAC: the streaming engine's response tail (fb_resp_tail_conv)
@@ -1342,7 +1341,8 @@ int fb_launch_resp(hz_fb* h, const double* d_in, double* d_out, long n) {
             h->ev_skip[h->ev.index_of(e) / 5] &= (unsigned char)~2;
         }
         for (int r = 0; r < rep; ++r)
-            launch_mac_lds(Qp, B, (const double2*)R.d_H.get(), (const double2*)R.d_Z.get(), (double2*)R.d_Y.get(), Q, h->stream);
+            HZ_TRY(launch_mac_lds(h->device, Qp, B, (const double2*)R.d_H.get(), (const double2*)R.d_Z.get(),
+                                  (double2*)R.d_Y.get(), Q, h->stream));
         HZ_TRY_HIP(hipGetLastError());
         if (e && inside) {
             HZ_TRY_HIP(hipEventRecord(e[2], h->stream));

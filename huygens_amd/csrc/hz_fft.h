@@ -15,9 +15,6 @@
 namespace hz {
 
 __device__ __forceinline__ void cmul_tw(double& r, double& i, double2 w, bool conj) {
-#if defined(HZ_STFT_ABLATE) && (HZ_STFT_ABLATE & 16)
-    w = make_double2(0.70710678118654752, -0.70710678118654752);
-#endif
     const double wi = conj ? -w.y : w.y;
     const double nr = r * w.x - i * wi;
     const double ni = r * wi + i * w.x;

@@ -453,22 +453,13 @@ inline void split_lg(int lg, int& lg1, int& lg2) {
     lg2 = lg - lg1;
 }
 
-template <typename K>
-inline void set_lds(K kern, size_t bytes) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
-inline void init_attrs() {
-    static bool done = false;
-    if (done) return;
-    const size_t b = col_lds(kMaxLg / 2);
-    set_lds(long_col_fwd_kernel<kIoStft>, b);
-    set_lds(long_col_fwd_kernel<kIoComplex>, b);
-    set_lds(long_col_fwd_kernel<kIoDct>, b);
-    set_lds(long_col_inv_kernel<kIoStft>, b);
-    set_lds(long_col_inv_kernel<kIoComplex>, b);
-    set_lds(long_col_inv_kernel<kIoDct>, b);
-    done = true;
+// the column kernels' dynamic-LDS limit, at the longest frame's size
+inline int init_attrs(int device) {
+    return hz::allow_lds(device,
+                         {(const void*)long_col_fwd_kernel<kIoStft>, (const void*)long_col_fwd_kernel<kIoComplex>,
+                          (const void*)long_col_fwd_kernel<kIoDct>, (const void*)long_col_inv_kernel<kIoStft>,
+                          (const void*)long_col_inv_kernel<kIoComplex>, (const void*)long_col_inv_kernel<kIoDct>},
+                         col_lds(kMaxLg / 2));
 }
 
 template <int IO>

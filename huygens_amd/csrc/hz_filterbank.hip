@@ -296,7 +296,7 @@ __global__ __launch_bounds__(wg_threads(PF)) void fb_mix_kernel(const double* __
                 for (int rw = 0; rw < 4; ++rw) {
 #pragma unroll
                     for (int i = 0; i < O; ++i) {
-                        double acc = readlane_d(z[i], 16 * rw + 15);
+                        double acc = lane_d(z[i], 16 * rw + 15);
 #pragma unroll
                         for (int q = 0; q < O; ++q) acc = fma(r[R::PL + i * O + q], C[rw][q], acc);
 #pragma unroll
@@ -505,20 +505,6 @@ __global__ __launch_bounds__(256) void fb_seg_carry_kernel(const double* __restr
     }
 }
 
-// out[t] = sum_g partial[g][t]
-__global__ __launch_bounds__(256) void fb_reduce_kernel(const double* __restrict__ partial, long n_pad,
-                                                        int G, long n, double* __restrict__ out) {
-    __shared__ double red[4][64];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const long t = (long)blockIdx.x * 64 + tx;
-    double s = 0.0;
-    if (t < n)
-        for (int g = ty; g < G; g += 4) s += partial[(long)g * n_pad + t];
-    red[ty][tx] = s;
-    __syncthreads();
-    if (ty == 0 && t < n) out[t] = (red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx]);
-}
-
 // ---------------------------------------------------------------------------
 // host-side precompute of a band record, in double-double (hz_dd.h): the homogeneous responses
 // h[k][j], M16, its powers; P[4] and P[5] keep their low words (the carries apply them many times)
@@ -711,14 +697,6 @@ int fb_prof_events(hz_fb* h, hipEvent_t** e) {
     return HZ_OK;
 }
 
-int fb_set_lds_attr(const void* k) {
-    static thread_local std::vector<const void*> done;
-    if (std::find(done.begin(), done.end(), k) != done.end()) return HZ_OK;
-    HZ_TRY_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    done.push_back(k);
-    return HZ_OK;
-}
-
 // staged setters -> device (the per-sample coefficient path, hz_fb_tv.hip, reads pin / gin)
 int fb_upload_staged(hz_fb* h) { return fb_upload(h); }
 
@@ -767,16 +745,14 @@ int fb_launch_general(hz_fb* h, const double* d_in, double* d_out, long n) {
     HZ_TRY(h->d_partial.reserve(need));
     MixKernel kmix = pick_kernel(O, h->dist_id, h->waves, h->bands_per_wave, MODE_MIX);
     MixKernel kend = pick_kernel(O, h->dist_id, h->waves, h->bands_per_wave, MODE_SEGEND);
-    HZ_TRY(fb_set_lds_attr((const void*)kmix));
+    HZ_TRY(hz::allow_lds(h->device, (const void*)kmix, kLdsCeiling));
     const size_t lds = lds_bytes(h->waves, true);
     const size_t lds_end = lds_bytes(h->waves, false);
     for (long off = 0; off < n; off += chunk) {
         const long len = std::min(chunk, n - off);
-        const long ntiles = (len + kTile - 1) / kTile;
         // time segments: enough workgroups to cover every CU at least once
-        long nseg = std::max<long>(1, std::min<long>(ntiles, (h->target_groups + G - 1) / G));
-        const long seg_tiles = (ntiles + nseg - 1) / nseg;
-        nseg = (ntiles + seg_tiles - 1) / seg_tiles;
+        const hz::MixPlan mp = hz::mix_plan(G, len, kTile, h->target_groups);
+        const long nseg = mp.nseg, seg_tiles = mp.seg_tiles;
         if (nseg > 1 && O > 0) HZ_TRY(h->d_seg.reserve((size_t)h->N * nseg * O));
         MixArgs a;
         a.rec = h->d_rec;
@@ -792,8 +768,8 @@ int fb_launch_general(hz_fb* h, const double* d_in, double* d_out, long n) {
         a.partial = h->d_partial;
         a.segstate = h->d_seg;
         a.n = len;
-        a.n_pad = ntiles * kTile;
-        a.seg_len = seg_tiles * kTile;
+        a.n_pad = mp.n_pad;
+        a.seg_len = mp.seg_len;
         a.nseg = (int)nseg;
         a.nbands = h->N;
         a.sp = h->sp;
@@ -824,8 +800,9 @@ int fb_launch_general(hz_fb* h, const double* d_in, double* d_out, long n) {
         HZ_TRY_HIP(hipGetLastError());
         if (e) HZ_TRY_HIP(hipEventRecord(e[2], h->stream));
         if (e) HZ_TRY_HIP(hipEventRecord(e[3], h->stream));
-        hipLaunchKernelGGL(fb_reduce_kernel, dim3((unsigned)((len + 63) / 64)), dim3(256), 0, h->stream,
-                           (const double*)h->d_partial, a.n_pad, G, len, d_out + off);
+        // out[t] = sum_g partial[g][t]
+        hz::mix::slab_reduce(h->stream, (const double*)h->d_partial, a.n_pad, G, len,
+                             hz::mix::SlabStore<double>{d_out + off});
         HZ_TRY_HIP(hipGetLastError());
         if (e) HZ_TRY_HIP(hipEventRecord(e[4], h->stream));
         h->xcur ^= 1;

@@ -547,19 +547,15 @@ int hz_frz_create(int N, int laps, double width, int device, hz_frz** out) {
     ok = ok && hipMemset(h->d_snap, 0, sizeof(double) * (N + 1)) == hipSuccess;   // Buffer zeroed
     ok = ok && hipMemcpy(h->d_win, win.data(), sizeof(double) * N, hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && hipMemcpy(h->d_tw, tw.data(), sizeof(double2) * (N / 2), hipMemcpyHostToDevice) == hipSuccess;
-    static bool attr = false;
-    if (ok && !attr) {
-        const int lds = (int)(sizeof(double) * 2 * kMaxN);
-        ok = hipFuncSetAttribute((const void*)frz_frame_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds) ==
-                 hipSuccess &&
-             hipFuncSetAttribute((const void*)frz_iframe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds) ==
-                 hipSuccess;
-        attr = ok;
-    }
     if (!ok) {
         hz::set_error("hz_frz_create: device allocation failed");
         delete h;
         return HZ_E_ALLOC;
+    }
+    if (int r = hz::allow_lds(device, {(const void*)frz_frame_kernel, (const void*)frz_iframe_kernel},
+                              sizeof(double) * 2 * kMaxN)) {
+        delete h;
+        return r;
     }
     *out = h;
     return HZ_OK;

@@ -108,14 +108,9 @@ __device__ __forceinline__ void osc_tick(double& zr, double& zi, double wr, doub
     // oscbank.h:61-62 (Eigen's complex packet product: re = ar br - ai bi, im = ar bi + ai br)
     const double r = zr * wr - zi * wi, m = zr * wi + zi * wr;
     const double nrm = (1.0 + (r * r + m * m)) / 2;
-#ifdef HZ_HET_PLAIN_DIV
-    zr = r / nrm;
-    zi = m / nrm;
-#else
     const double y = rcp_newton(nrm);
     zr = div_with(r, nrm, y);
     zi = div_with(m, nrm, y);
-#endif
 }
 
 // O Slidebank stages, S Stickbank taps (compile-time: only the live state occupies VGPRs);

@@ -228,7 +228,7 @@ constexpr int kTPad = kTT + 1;  // tile row stride: lane-major writes and time-m
 // with ft = mtof(position in effect), recomputed only when a step happened.  A wave's 64 partials x
 // 64 samples are transposed through a padded LDS tile; lanes then become time and sum the partials
 // in index order, so a sample's sum does not depend on how a call is split.  One wave per workgroup
-// (a 64 x 256 bank is 256 workgroups, one per CU); each writes one group row for add_reduce_kernel.
+// (a 64 x 256 bank is 256 workgroups, one per CU); each writes one group row for hz_mix.h's slab reduce.
 __global__ __launch_bounds__(64) void add_track_kernel(hz::TrackArgs a) {
     __shared__ double tile[64 * kTPad];
     const int lane = threadIdx.x;

@@ -27,14 +27,15 @@
 #include <vector>
 
 #include "hz_common.h"
+#include "hz_mix.h"
+#include "hz_mixplan.h"
 
 namespace {
 
+using namespace hz::mix;   // kWaves, kMaxPerWave, kPad, cmul and the end-of-tile / slab reductions
+
 constexpr int kL = 16;
-constexpr int kTile = 64 * kL;
-constexpr int kWaves = 8;          // waves per workgroup
-constexpr int kMaxPerWave = 64;    // partials per wave per tile (upper bound)
-constexpr int kPad = 66;           // LDS row pad (conflict-free transposed reads)
+constexpr int kTile = tile_len(kL);
 
 // per-partial record (doubles): w, T1[16] = (w^16)^p, T2[4] = (w^256)^r, W = w^1024
 struct ORec {
@@ -52,13 +53,6 @@ struct OscArgs {
     long n, n_pad, seg_len;
     int A, nseg, per_wave;
 };
-
-__device__ __forceinline__ void cmul(double ar, double ai, double br, double bi, double& cr, double& ci) {
-    const double r = fma(ar, br, -ai * bi);
-    const double i = fma(ar, bi, ai * br);
-    cr = r;
-    ci = i;
-}
 
 __global__ __launch_bounds__(64 * kWaves) void osc_mix_kernel(const double* __restrict__ rec, OscArgs a) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -123,57 +117,12 @@ __global__ __launch_bounds__(64 * kWaves) void osc_mix_kernel(const double* __re
                 cmul(sr, si, wr, wi, sr, si);
             }
         }
-        // ---- workgroup reduction over waves -----------------------------------
-        double* mr = part_re + wave * (kL * kPad);
-        double* mi = part_im + wave * (kL * kPad);
-#pragma unroll
-        for (int j = 0; j < kL; ++j) {
-            mr[j * kPad + lane] = accr[j];
-            mi[j * kPad + lane] = acci[j];
-        }
-        __syncthreads();
-        for (int tl = threadIdx.x; tl < kTile; tl += blockDim.x) {
-            const int src = tl >> 4, j = tl & 15;
-            double sr0 = 0.0, si0 = 0.0;
-#pragma unroll
-            for (int w = 0; w < kWaves; ++w) {
-                sr0 += part_re[w * (kL * kPad) + j * kPad + src];
-                si0 += part_im[w * (kL * kPad) + j * kPad + src];
-            }
-            const long t = t0 + tl;
-            if (t < a.n) {
-                double2 v;
-                v.x = sr0;
-                v.y = si0;
-                reinterpret_cast<double2*>(a.partial)[(long)blockIdx.x * a.n_pad + t] = v;
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// mix[t] = sum_g partial[g][t]   (complex, interleaved)
-__global__ __launch_bounds__(256) void osc_reduce_kernel(const double2* __restrict__ partial, long n_pad, int G,
-                                                         long n, double2* __restrict__ mix) {
-    __shared__ double2 red[4][64];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const long t = (long)blockIdx.x * 64 + tx;
-    double2 s;
-    s.x = 0.0;
-    s.y = 0.0;
-    if (t < n)
-        for (int g = ty; g < G; g += 4) {
-            const double2 v = partial[(long)g * n_pad + t];
-            s.x += v.x;
-            s.y += v.y;
-        }
-    red[ty][tx] = s;
-    __syncthreads();
-    if (ty == 0 && t < n) {
-        double2 o;
-        o.x = (red[0][tx].x + red[1][tx].x) + (red[2][tx].x + red[3][tx].x);
-        o.y = (red[0][tx].y + red[1][tx].y) + (red[2][tx].y + red[3][tx].y);
-        mix[t] = o;
+        // ---- workgroup reduction over waves (hz_mix.h) ----------------------------
+        put_rows<kL>(part_re + wave * (kL * kPad), lane, accr);
+        put_rows<kL>(part_im + wave * (kL * kPad), lane, acci);
+        tile_reduce<kL, 2>(part_re, t0, a.n, [&](long t, const double (&s)[2]) {
+            reinterpret_cast<double2*>(a.partial)[(long)blockIdx.x * a.n_pad + t] = make_double2(s[0], s[1]);
+        });
     }
 }
 
@@ -328,35 +277,26 @@ int osc_launch(hz_osc* h, double* d_mix, double* d_per_band, long n) {
         // partials per wave and groups: few partial rows, then time segments to fill the CUs
         int per_wave = std::min(kMaxPerWave, std::max(1, (A + kWaves * 32 - 1) / (kWaves * 32)));
         const int G = (A + kWaves * per_wave - 1) / (kWaves * per_wave);
-        const long ntiles = (n + kTile - 1) / kTile;
-        long nseg = std::max<long>(1, std::min<long>(ntiles, (h->target_groups + G - 1) / G));
-        const long seg_tiles = (ntiles + nseg - 1) / nseg;
-        nseg = (ntiles + seg_tiles - 1) / seg_tiles;
-        const long n_pad = ntiles * kTile;
-        const size_t need = (size_t)G * n_pad * 2;
+        const hz::MixPlan mp = hz::mix_plan(G, n, kTile, h->target_groups);
+        const size_t need = (size_t)G * mp.n_pad * 2;
         HZ_TRY(h->d_partial.reserve(need));
-        const size_t lds = sizeof(double) * (2 * kWaves * kL * kPad + kWaves * 2 * kMaxPerWave);
-        static bool attr = false;
-        if (!attr) {
-            HZ_TRY_HIP(hipFuncSetAttribute((const void*)osc_mix_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds));
-            attr = true;
-        }
+        const size_t lds = sizeof(double) * (2 * plane_len(kL) + kWaves * 2 * kMaxPerWave);
+        HZ_TRY(hz::allow_lds(h->device, (const void*)osc_mix_kernel, lds));
         OscArgs a;
         a.act = h->d_act;
         a.z0 = h->d_z;
         a.partial = h->d_partial;
         a.n = n;
-        a.n_pad = n_pad;
-        a.seg_len = seg_tiles * kTile;
+        a.n_pad = mp.n_pad;
+        a.seg_len = mp.seg_len;
         a.A = A;
-        a.nseg = (int)nseg;
+        a.nseg = (int)mp.nseg;
         a.per_wave = per_wave;
-        hipLaunchKernelGGL(osc_mix_kernel, dim3(G, (unsigned)nseg), dim3(64 * kWaves), lds, h->stream,
+        hipLaunchKernelGGL(osc_mix_kernel, dim3(G, (unsigned)mp.nseg), dim3(64 * kWaves), lds, h->stream,
                            (const double*)h->d_rec, a);
         HZ_TRY_HIP(hipGetLastError());
-        hipLaunchKernelGGL(osc_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, h->stream,
-                           (const double2*)h->d_partial.get(), n_pad, G, n, (double2*)d_mix);
+        // mix[t] = sum_g partial[g][t]   (complex, interleaved)
+        slab_reduce(h->stream, (const double2*)h->d_partial.get(), mp.n_pad, G, n, SlabStore<double2>{(double2*)d_mix});
         HZ_TRY_HIP(hipGetLastError());
     }
     if (e) HZ_TRY_HIP(hipEventRecord(e[1], h->stream));

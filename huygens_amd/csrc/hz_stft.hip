@@ -40,12 +40,6 @@
 #include "hz_fft_long.h"
 #include "hz_transpose.h"
 
-// Experiment builds only (-DHZ_STFT_ABLATE=mask; wrong results): 1 skip the processor,
-// 2 skip the inverse FFT, 4 skip the forward FFT, 8 skip the ring store, 16 twiddles = tw[0].
-#ifndef HZ_STFT_ABLATE
-#define HZ_STFT_ABLATE 0
-#endif
-
 namespace {
 
 constexpr int kThreads = 1024;       // DCT workgroups: one radix-4 butterfly per thread at N = 4096
@@ -194,11 +188,11 @@ __device__ __forceinline__ void frame_middle(double* re, double* im, int lg, dou
             xr[j] = re[hz::pad16(e0 + j)];
             xi[j] = im[hz::pad16(e0 + j)];
         }
-        if constexpr (!(HZ_STFT_ABLATE & 4)) hz::dif_regs<R, false>(xr, xi, lg, R - 1, 0, T);
+        hz::dif_regs<R, false>(xr, xi, lg, R - 1, 0, T);
     }
-    if constexpr (!(HZ_STFT_ABLATE & 1)) apply_proc<PROC, M>(xr, xi, act, e0, 1 << lg, p0, p1, scratch);
+    apply_proc<PROC, M>(xr, xi, act, e0, 1 << lg, p0, p1, scratch);
     if (act) {
-        if constexpr (!(HZ_STFT_ABLATE & 2)) hz::dit_regs<R, false>(xr, xi, lg, 0, 0, T);
+        hz::dit_regs<R, false>(xr, xi, lg, 0, 0, T);
 #pragma unroll
         for (int j = 0; j < M; ++j) {
             re[hz::pad16(e0 + j)] = xr[j];
@@ -361,18 +355,17 @@ __global__ __launch_bounds__(kFrameThreads) void stft_frame_kernel(StftArgs a) {
     } else if constexpr (MODE == 2) {
         hz::fft_inv_tail<RMAX>(re, im, lg, T, true);
     } else {
-        if constexpr (!(HZ_STFT_ABLATE & 4)) hz::fft_fwd_lead<RMAX>(re, im, lg, T, false);
+        hz::fft_fwd_lead<RMAX>(re, im, lg, T, false);
         switch (hz::fft_rlast<RMAX>(lg)) {
         case 4: if constexpr (RMAX >= 4) frame_middle_of<4, PROC>(re, im, lg, a.p0, a.p1, scratch, T); break;
         case 3: frame_middle_of<3, PROC>(re, im, lg, a.p0, a.p1, scratch, T); break;
         default: frame_middle_of<2, PROC>(re, im, lg, a.p0, a.p1, scratch, T); break;   // N = 4
         }
         __syncthreads();
-        if constexpr (!(HZ_STFT_ABLATE & 2)) hz::fft_inv_tail<RMAX>(re, im, lg, T, false);
+        hz::fft_inv_tail<RMAX>(re, im, lg, T, false);
     }
     double* out = a.fo + (f % a.R) * N;
     const long plane = (long)a.R * N;
-    if constexpr ((HZ_STFT_ABLATE & 8) != 0) return;
     for (int k = threadIdx.x; k < N; k += blockDim.x) {
         const int e = hz::pad16(k);
         out[k] = re[e];
@@ -1307,11 +1300,9 @@ long frames_before(const hz_stft* h, long T) {
 }
 
 template <int PROC, int MODE>
-void frame_attr(int lds) {
-    (void)hipFuncSetAttribute((const void*)stft_frame_kernel<PROC, MODE, 3>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)stft_frame_kernel<PROC, MODE, 4>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+int frame_attr(int device, size_t lds) {
+    return hz::allow_lds(device, {(const void*)stft_frame_kernel<PROC, MODE, 3>,
+                                  (const void*)stft_frame_kernel<PROC, MODE, 4>}, lds);
 }
 
 template <int PROC, int MODE>
@@ -1325,30 +1316,19 @@ void launch_frames(hz_stft* h, const StftArgs& a, long nf) {
 }
 
 template <int PROC>
-void launch_pairs(hz_stft* h, const StftArgs& a, long nf) {
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)stft_pair_kernel<PROC, 3>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)frame_lds(kMaxN));
-        (void)hipFuncSetAttribute((const void*)stft_pair_kernel<PROC, 4>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)frame_lds(kMaxN));
-        attr = true;
-    }
-    if (h->N == p4::kN) {
-        static bool attr4 = false;
-        if (!attr4) {
-            (void)hipFuncSetAttribute((const void*)stft_pair4096_kernel<PROC>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)p4::lds_bytes());
-            attr4 = true;
-        }
+int launch_pairs(hz_stft* h, const StftArgs& a, long nf) {   // (the launch error is the caller's to read)
+    HZ_TRY(hz::allow_lds(h->device, {(const void*)stft_pair4096_kernel<PROC>, (const void*)stft_pair_kernel<PROC, 3>,
+                                     (const void*)stft_pair_kernel<PROC, 4>}, frame_lds(kMaxN)));
+    if (h->N == p4::kN)
         hipLaunchKernelGGL((stft_pair4096_kernel<PROC>), dim3((unsigned)((nf + 1) / 2)), dim3(p4::kT), p4::lds_bytes(),
                            h->stream, a, nf);
-    } else if (frame_rmax(h->N) == 3)
+    else if (frame_rmax(h->N) == 3)
         hipLaunchKernelGGL((stft_pair_kernel<PROC, 3>), dim3((unsigned)((nf + 1) / 2)), dim3(frame_threads(h->N)),
                            frame_lds(h->N), h->stream, a, nf);
     else
         hipLaunchKernelGGL((stft_pair_kernel<PROC, 4>), dim3((unsigned)((nf + 1) / 2)), dim3(frame_threads(h->N)),
                            frame_lds(h->N), h->stream, a, nf);
+    return HZ_OK;
 }
 
 // real input and a magnitude gate: two frames per transform (stft_pair_kernel)
@@ -1423,8 +1403,8 @@ int long_frames(hz_stft* h, const StftArgs& a, long nf, int mode) {
 int frames_fused(hz_stft* h, const StftArgs& a, long nf) {
     if (h->N > kMaxN) return long_frames(h, a, nf, 0);
     if (pair_launch(h, a)) {
-        if (h->proc == HZ_PROC_STATIC_GATE) launch_pairs<HZ_PROC_STATIC_GATE>(h, a, nf);
-        else launch_pairs<HZ_PROC_GATE_KEEP>(h, a, nf);
+        if (h->proc == HZ_PROC_STATIC_GATE) HZ_TRY(launch_pairs<HZ_PROC_STATIC_GATE>(h, a, nf));
+        else HZ_TRY(launch_pairs<HZ_PROC_GATE_KEEP>(h, a, nf));
         HZ_TRY_HIP(hipGetLastError());
         return HZ_OK;
     }
@@ -1682,29 +1662,28 @@ int stft_create(const char* who, int max_n, int N, int laps, int window, int pro
         ok = ok && hipMemcpy(h->d_tw1, t1.data(), sizeof(double2) * t1.size(), hipMemcpyHostToDevice) == hipSuccess;
         ok = ok && hipMemcpy(h->d_tw2, t2.data(), sizeof(double2) * t2.size(), hipMemcpyHostToDevice) == hipSuccess;
         ok = ok && h->d_ws.reserve((size_t)N) == HZ_OK;
-        hzl::init_attrs();
     }
     if (!ok) {
         hz::set_error("%s: device allocation failed", who);
         delete h;
         return HZ_E_ALLOC;
     }
-    static bool attr = false;
-    if (!attr) {   // padded frame: 2 (N + N/16) doubles of LDS per workgroup (136 KB at N = 8192)
-        const int lds = (int)std::max(frame_lds(kMaxN), sizeof(double) * (2 * kMaxN + 2 * (kThreads / 64)));
-        frame_attr<HZ_PROC_IDENTITY, 0>(lds);
-        frame_attr<HZ_PROC_STATIC_GATE, 0>(lds);
-        frame_attr<HZ_PROC_GATE_KEEP, 0>(lds);
-        frame_attr<HZ_PROC_HILBERT, 0>(lds);
-        frame_attr<HZ_PROC_TRANSPOSE, 0>(lds);
-        frame_attr<HZ_PROC_IDENTITY, 1>(lds);
-        frame_attr<HZ_PROC_IDENTITY, 2>(lds);
-        for (const void* k : {(const void*)slot_fft_kernel<3, false>, (const void*)slot_fft_kernel<3, true>,
-                              (const void*)slot_fft_kernel<4, false>, (const void*)slot_fft_kernel<4, true>})
-            (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        (void)hipFuncSetAttribute((const void*)dct2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        (void)hipFuncSetAttribute((const void*)dct3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr = true;
+    // padded frame: 2 (N + N/16) doubles of LDS per workgroup (136 KB at N = 8192)
+    const size_t lds = frame_lds(kMaxN);
+    int r = N > kMaxN ? hzl::init_attrs(device) : HZ_OK;
+    if (!r) r = frame_attr<HZ_PROC_IDENTITY, 0>(device, lds);
+    if (!r) r = frame_attr<HZ_PROC_STATIC_GATE, 0>(device, lds);
+    if (!r) r = frame_attr<HZ_PROC_GATE_KEEP, 0>(device, lds);
+    if (!r) r = frame_attr<HZ_PROC_HILBERT, 0>(device, lds);
+    if (!r) r = frame_attr<HZ_PROC_TRANSPOSE, 0>(device, lds);
+    if (!r) r = frame_attr<HZ_PROC_IDENTITY, 1>(device, lds);
+    if (!r) r = frame_attr<HZ_PROC_IDENTITY, 2>(device, lds);
+    if (!r)
+        r = hz::allow_lds(device, {(const void*)slot_fft_kernel<3, false>, (const void*)slot_fft_kernel<3, true>,
+                                   (const void*)slot_fft_kernel<4, false>, (const void*)slot_fft_kernel<4, true>}, lds);
+    if (r) {
+        delete h;
+        return r;
     }
     *out = h;
     return HZ_OK;
@@ -2164,12 +2143,18 @@ int hz_dct_create(int N, int device, hz_dct** out) {
         ok = ok && hipMemcpy(h->d_tw1, t1.data(), sizeof(double2) * t1.size(), hipMemcpyHostToDevice) == hipSuccess;
         ok = ok && hipMemcpy(h->d_tw2, t2.data(), sizeof(double2) * t2.size(), hipMemcpyHostToDevice) == hipSuccess;
         ok = ok && h->d_ws.reserve((size_t)N) == HZ_OK;
-        hzl::init_attrs();
     }
     if (!ok) {
         hz::set_error("hz_dct_create: allocation failed");
         delete h;
         return HZ_E_ALLOC;
+    }
+    // dct_launch's dynamic LDS: the column kernels' ceiling, or the frame of dct2_kernel / dct3_kernel
+    if (int r = N > kMaxN ? hzl::init_attrs(device)
+                          : hz::allow_lds(device, {(const void*)dct2_kernel, (const void*)dct3_kernel},
+                                          sizeof(double) * 2 * (size_t)N)) {
+        delete h;
+        return r;
     }
     std::memset(h->h_in, 0, sizeof(double) * N);
     std::memset(h->h_out, 0, sizeof(double) * N);

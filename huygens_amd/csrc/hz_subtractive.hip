@@ -28,7 +28,7 @@
 //      round's last tick; a round's input, envelope and coefficients are fetched one round ahead)
 //      the lanes' weighted outputs are summed through LDS (hz_fb_tv.hip's rounds: 16-value runs,
 //      an xor tree over 4 lanes) into partial rows [groups][N][n];
-//   5. sub_reduce_kernel sums the group rows (one group: the resonator writes the output itself).
+//   5. hz_mix.h's slab reduce sums the group rows (one group: the resonator writes the output itself).
 // Filter state and the coefficients last set persist in the handle across calls, note events and
 // a stolen voice (the reference never calls forget()).
 #include <algorithm>
@@ -39,6 +39,7 @@
 
 #include "hz_common.h"
 #include "hz_minimizer.h"
+#include "hz_mix.h"
 #include "hz_resonant.h"
 
 namespace {
@@ -215,21 +216,6 @@ __global__ __launch_bounds__(kThreads) void sub_res_kernel(ResArgs a) {
     }
 }
 
-// out[k][t] = sum of the group rows (add_reduce_kernel's pattern, a channel per blockIdx.y)
-__global__ __launch_bounds__(256) void sub_reduce_kernel(const double* __restrict__ part, long pstride, int G, int N,
-                                                         long n, double* __restrict__ out, long ostride) {
-    __shared__ double red[4][64];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int ch = blockIdx.y;
-    const long t = (long)blockIdx.x * 64 + tx;
-    double s = 0.0;
-    if (t < n)
-        for (int g = ty; g < G; g += 4) s += part[((size_t)g * N + ch) * pstride + t];
-    red[ty][tx] = s;
-    __syncthreads();
-    if (ty == 0 && t < n) out[(size_t)ch * ostride + t] = (red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx]);
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -369,8 +355,9 @@ int sub_audio(hz_sub* h, const double* d_x, long xstride, double* d_dst, long os
 int sub_reduce(hz_sub* h, double* d_dst, long ostride, long n) {
     const int P = h->V * h->O, G = (P + kThreads - 1) / kThreads;
     if (G <= 1) return HZ_OK;
-    hipLaunchKernelGGL(sub_reduce_kernel, dim3((unsigned)((n + 63) / 64), h->N), dim3(256), 0, h->stream,
-                       (const double*)h->d_part, n, G, h->N, n, d_dst, ostride);
+    // out[k][t] = sum of the group rows, a channel per blockIdx.y
+    hz::mix::slab_reduce(h->stream, (const double*)h->d_part, n, G, n, hz::mix::SlabChannel{h->N, d_dst, ostride},
+                         (unsigned)h->N);
     HZ_TRY_HIP(hipGetLastError());
     return HZ_OK;
 }

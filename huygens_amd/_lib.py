@@ -86,6 +86,8 @@ _SIGS = {
     "hz_fb_sample_info": (I, [VP, C.POINTER(I), C.POINTER(C.c_longlong), C.POINTER(I)]),
     "hz_fb_process_tv": (I, [VP, PD, PD, SZ, I, PD, D]),
     "hz_fb_process_tv_device": (I, [VP, VP, VP, SZ, I, VP, D]),
+    "hz_fb_process_events": (I, [VP, PD, PD, SZ, VP, I]),
+    "hz_fb_process_events_device": (I, [VP, VP, VP, SZ, VP, I]),
     "hz_fb_set_stream": (I, [VP, VP]),
     "hz_fb_get_stream": (I, [VP, C.POINTER(VP)]),
     "hz_fb_synchronize": (I, [VP]),

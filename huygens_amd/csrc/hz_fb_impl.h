@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "hz_common.h"
+#include "hz_fb_events.h"
 #include "hz_mix.h"
 #include "hz_mixplan.h"
 
@@ -106,6 +107,13 @@ struct hz_fb {
     hz::DevBuf<double> d_seg;  // segment start states
     int target_groups = 256;  // workgroups wanted per launch (CU count)
     hz::DevBuf<double> d_in, d_out;
+    // hz_fb_process_events: the piece's compiled rows (hz_fb_events.h: offsets, then rows), staged
+    // in pinned memory; ev_up marks the copy's end (the staging is rewritten by the next piece)
+    hz_fbev::Plan ev_plan;
+    hz::DevBuf<char> d_ev;
+    hz::PinBuf<char> h_ev;
+    hz::Event ev_up;
+    bool ev_up_pending = false;
     // host-buffer calls that take the streaming engine: pinned, device-mapped staging the kernel
     // reads and writes directly ([kStreamBlock] in, then [kStreamBlock] out, then 128 completion
     // flags (long long))
@@ -363,7 +371,10 @@ void fb_mirror_sync_band(hz_fb* h, int l);   // band l only (before a one-band s
 // a target setter advances pg_gen: l = its local band, -1 = a band of another shard, kAllBands = all
 constexpr int kAllBands = -2;
 void fb_rt_target_setter(hz_fb* h, int l);
-int fb_launch_general(hz_fb* h, const double* d_in, double* d_out, long n);
+// ev_rows non-null: the event form over the compiled rows of one hz_fb_process_events piece
+// (device pointers; n within one launch)
+int fb_launch_general(hz_fb* h, const double* d_in, double* d_out, long n, const int* ev_off = nullptr,
+                      const double* ev_rows = nullptr);
 int fb_upload_staged(hz_fb* h);              // staged setters -> device
 int fb_tv_materialize(hz_fb* h);             // pending stream row -> F/B (hz_fb_tv.hip)
 // hz_fb_lti.hip

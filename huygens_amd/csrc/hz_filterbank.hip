@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "hz_dd.h"
+#include "hz_fb_events.h"
 #include "hz_fb_impl.h"
 
 namespace {
@@ -86,6 +87,14 @@ struct MixArgs {
     double dist_param;
 };
 
+// the event form's arguments (fb_mix_kernel<.., EV = true>, hz_fb_events.h): rows of band b are
+// [ev_off[b], ev_off[b + 1]) of ev_rows.  A type of its own: the plain kernels keep their
+// argument block as it was.
+struct MixArgsEv : MixArgs {
+    const int* ev_off;
+    const double* ev_rows;
+};
+
 // LDS layout of one workgroup:
 //   xs   : the tile's input x[t0-16 .. t0+1023], padded one slot per 16 samples so
 //          lane c's reads (17c + k) hit 64 distinct banks (ds_read_b64)
@@ -112,8 +121,38 @@ __device__ __forceinline__ int xs_pos(int li) { return li + (li >> 4); }
 // wave interleaved for ILP instead of occupancy).
 constexpr int wg_threads(int PF) { return PF == 2 ? 1024 : (PF == 3 ? 512 : 256); }
 
-template <int O, int DIST, int NB, int MODE, int PF>
-__global__ __launch_bounds__(wg_threads(PF)) void fb_mix_kernel(const double* __restrict__ rec, MixArgs a) {
+// s^d for an integer-valued distance d >= 0 by binary powering in double-double (hz_dd.h): a rolled
+// loop over a few registers, where the library's FP64 pow raised every event instantiation's peak
+// by 30-40 VGPRs; 1 at d = 0, also for s = 0 (an instant smoother)
+__device__ __forceinline__ double pow_steps(double s, double d) {
+    hz_dd::dd r{1.0, 0.0}, b{s, 0.0};
+#pragma nounroll
+    for (unsigned long long e = (unsigned long long)d; e > 0; e >>= 1) {
+        if (e & 1) r = hz_dd::mul(r, b);
+        b = hz_dd::mul(b, b);
+    }
+    return r.hi;
+}
+
+template <bool B>
+using tag_b = std::integral_constant<int, B ? 1 : 0>;
+using tag_walk = std::integral_constant<int, 2>;
+
+// EV (one band per wave): the event form of hz_fb_process_events.  A band that has rows (target
+// changes at samples t_k, hz_fb_events.h) takes its targets and smoother seeds from the row in
+// force instead of pin / gin / pgstate: a wave-uniform cursor follows the rows tile by tile; a
+// tile no row starts in runs the code below with that row's values (the converged fast paths
+// included), and a tile with a row inside steps both smoothers per lane through the rows first
+// (ev_walk, values through the wave's own LDS rows) and reads them back sample by sample.  A band
+// without rows, and every EV = false instantiation, runs the code as it was.
+template <int O, int DIST, int NB, int MODE, int PF, bool EV = false>
+__global__ __launch_bounds__(wg_threads(PF)) void fb_mix_kernel(const double* __restrict__ rec,
+                                                                std::conditional_t<EV, MixArgsEv, MixArgs> a) {
+    static_assert(!EV || NB == 1, "the event form is built for one band per wave");
+    constexpr int kRow = hz_fbev::kRow;
+    const int* ev_off = nullptr;
+    const double* ev_rows = nullptr;
+    if constexpr (EV) ev_off = a.ev_off, ev_rows = a.ev_rows;
     // rec is passed as its own __restrict__ argument so the compiler can prove the
     // kernel's stores never clobber it: wave-uniform record reads become s_load.
     using R = Rec<O>;
@@ -163,6 +202,44 @@ __global__ __launch_bounds__(wg_threads(PF)) void fb_mix_kernel(const double* __
         gin[b] = live[b] ? a.gin[bb] : 0.0;
     }
 
+    // event form: the band's rows, the row in force at the tile start (ecur) and the next row's
+    // time (etn), wave-uniform; sp_t / sg_t then count from that row: s^(t0 - t_ecur)
+    int er1 = 0, ecur = 0;
+    bool evb = false;
+    double etn = 0.0;
+    if constexpr (EV) {
+        if (live[0]) {
+            ecur = __builtin_amdgcn_readfirstlane(ev_off[band0]);
+            er1 = __builtin_amdgcn_readfirstlane(ev_off[band0 + 1]);
+        }
+        evb = er1 > ecur;   // (a band with rows has at least two: t = 0 and t = n)
+        if (evb) etn = uniform(ev_rows[(long)(ecur + 1) * kRow]);
+    }
+    // both smoothers of a lane through the rows of its 16 samples, into the wave's LDS rows:
+    // which = 0 pre (s = sp), 1 gain (s = sg); w_cur = s^(tc - t_ecur)
+    auto ev_walk = [&](int which, double s, double w_cur, long tc) {
+        const double* rows = ev_rows;
+        const double tcd = (double)tc;
+        int k = ecur;
+        while (k + 1 < er1 && rows[(long)(k + 1) * kRow] <= tcd) ++k;   // the row in force at tc
+        const double* rw = rows + (long)k * kRow;
+        double tgt = rw[hz_fbev::kPin + which];
+        const double d = tcd - rw[hz_fbev::kT];
+        const double w = k == ecur ? w_cur : pow_steps(s, d);
+        double v = tgt + w * (rw[hz_fbev::kP + which] - tgt);
+        double tn = k + 1 < er1 ? rows[(long)(k + 1) * kRow] : HUGE_VAL;
+#pragma nounroll
+        for (int j = 0; j < kL; ++j) {
+            while (tcd + j >= tn) {
+                ++k;
+                tgt = rows[(long)k * kRow + hz_fbev::kPin + which];
+                tn = k + 1 < er1 ? rows[(long)(k + 1) * kRow] : HUGE_VAL;
+            }
+            v = fma(s, v, (1.0 - s) * tgt);
+            my[j * kPartPad + lane] = v;
+        }
+    };
+
     // input tiles are double-buffered in LDS; tile k+1 is loaded into registers while
     // tile k computes and written to the other buffer before the tile's barrier
     // PF = x values per thread = ceil(1040 / blockDim)
@@ -202,6 +279,29 @@ __global__ __launch_bounds__(wg_threads(PF)) void fb_mix_kernel(const double* __
         const bool more = tile + 1 < ntiles;
         if (more) load_x(t0 + kTile, pf);  // in flight during this tile's compute
 
+        [[maybe_unused]] bool walk = false;   // a row starts inside this tile after its first sample
+        if constexpr (EV) {
+            if (evb) {
+                bool moved = tile == 0;
+                while (etn <= (double)t0) {
+                    ++ecur;
+                    etn = ecur + 1 < er1 ? uniform(ev_rows[(long)(ecur + 1) * kRow]) : HUGE_VAL;
+                    moved = true;
+                }
+                if (moved) {
+                    const double* rw = ev_rows + (long)ecur * kRow;
+                    pin[0] = uniform(rw[hz_fbev::kPin]);
+                    gin[0] = uniform(rw[hz_fbev::kGin]);
+                    P0[0] = uniform(rw[hz_fbev::kP]);
+                    G0[0] = uniform(rw[hz_fbev::kG]);
+                    const double d = (double)t0 - uniform(rw[hz_fbev::kT]);
+                    sp_t = uniform(pow_steps(a.sp, d));   // (else: advanced by a tile at the loop's end)
+                    sg_t = uniform(pow_steps(a.sg, d));
+                }
+                walk = etn < (double)(t0 + kTile);
+            }
+        }
+
         // ---- zero-state pass over the lane's 16 samples, all NB bands ----------
         // Fast path once the pre-amp smoother has converged for this tile
         // (sp^t |P0 - pin| <= 2^-60 |pin|: pre == pin to ~1e-18): pin folds into b.
@@ -212,8 +312,9 @@ __global__ __launch_bounds__(wg_threads(PF)) void fb_mix_kernel(const double* __
             gfast = gfast && (sg_t * fabs(G0[b] - gin[b]) <= 0x1p-60 * fabs(gin[b]));
         }
         double zsr[NB][kL];
-        auto zsr_pass = [&](auto fast_tag) {
-            constexpr bool FAST = decltype(fast_tag)::value;
+        auto zsr_pass = [&](auto tag) {
+            constexpr bool FAST = decltype(tag)::value == 1;
+            constexpr bool WALK = decltype(tag)::value == 2;   // pre[t] from ev_walk's LDS rows
             double xw[O + 1];  // x[t], x[t-1], ... sliding window
 #pragma unroll
             for (int k = 1; k <= O; ++k) xw[k] = xs[17 * lane + 16 - k];
@@ -239,7 +340,8 @@ __global__ __launch_bounds__(wg_threads(PF)) void fb_mix_kernel(const double* __
                     for (int i = 1; i <= O; ++i) ff = fma(bp[b][i], xw[i], ff);
                     double y = ff;
                     if constexpr (!FAST) {
-                        pre[b] = fma(a.sp, pre[b], (1.0 - a.sp) * pin[b]);
+                        if constexpr (WALK) pre[b] = my[j * kPartPad + lane];
+                        else pre[b] = fma(a.sp, pre[b], (1.0 - a.sp) * pin[b]);
                         y = ff * pre[b];
                     }
 #pragma unroll
@@ -253,8 +355,16 @@ __global__ __launch_bounds__(wg_threads(PF)) void fb_mix_kernel(const double* __
                 for (int k = O; k > 0; --k) xw[k] = xw[k - 1];
             }
         };
-        if (pfast) zsr_pass(std::true_type{});
-        else zsr_pass(std::false_type{});
+        if constexpr (EV) {
+            if (walk) {
+                ev_walk(0, a.sp, sp_lane * sp_t, tc);
+                zsr_pass(tag_walk{});
+            } else if (pfast) zsr_pass(tag_b<true>{});
+            else zsr_pass(tag_b<false>{});
+        } else {
+            if (pfast) zsr_pass(tag_b<true>{});
+            else zsr_pass(tag_b<false>{});
+        }
 
         // ---- carry scan across the 64 chunks of the tile -----------------------
         //   1. intra-row (16 lanes) inclusive scan of the chunk end states with DPP
@@ -327,8 +437,9 @@ __global__ __launch_bounds__(wg_threads(PF)) void fb_mix_kernel(const double* __
             // correction c = y - zsr obeys the homogeneous recurrence seeded with the
             // chunk start state: c_j = -sum_k a_k c_{j-1-k}, c_{-1-k} = st[k].
             // Gain fast path once the gain smoother has converged (as for pre).
-            auto fix_pass = [&](auto fast_tag) {
-                constexpr bool FAST = decltype(fast_tag)::value;
+            auto fix_pass = [&](auto tag) {
+                constexpr bool FAST = decltype(tag)::value == 1;
+                constexpr bool WALK = decltype(tag)::value == 2;   // gain[t] from ev_walk's LDS rows
                 double g[NB], cr[NB][O > 0 ? O : 1];
 #pragma unroll
                 for (int b = 0; b < NB; ++b) {
@@ -352,7 +463,8 @@ __global__ __launch_bounds__(wg_threads(PF)) void fb_mix_kernel(const double* __
                             cr[b][0] = c;
                             y += c;
                         }
-                        if constexpr (!FAST) g[b] = fma(a.sg, g[b], (1.0 - a.sg) * gin[b]);
+                        if constexpr (WALK) g[b] = my[j * kPartPad + lane];   // (read before v goes there)
+                        else if constexpr (!FAST) g[b] = fma(a.sg, g[b], (1.0 - a.sg) * gin[b]);
                         double gy = g[b] * y;
                         // (saturate / limiter with one band per wave: on the LDS row below, after the
                         // recurrence registers are dead -- inline here they spilled them: C2 bank
@@ -365,8 +477,16 @@ __global__ __launch_bounds__(wg_threads(PF)) void fb_mix_kernel(const double* __
                     my[j * kPartPad + lane] = v;
                 }
             };
-            if (gfast) fix_pass(std::true_type{});
-            else fix_pass(std::false_type{});
+            if constexpr (EV) {
+                if (walk) {
+                    ev_walk(1, a.sg, sg_lane * sg_t, tc);
+                    fix_pass(tag_walk{});
+                } else if (gfast) fix_pass(tag_b<true>{});
+                else fix_pass(tag_b<false>{});
+            } else {
+                if (gfast) fix_pass(tag_b<true>{});
+                else fix_pass(tag_b<false>{});
+            }
             if (NB == 1 && !live[0]) {  // wave-uniform: padding wave past the last band
 #pragma unroll
                 for (int j = 0; j < kL; ++j) my[j * kPartPad + lane] = 0.0;
@@ -399,6 +519,14 @@ __global__ __launch_bounds__(wg_threads(PF)) void fb_mix_kernel(const double* __
 #pragma unroll
                         for (int k = 0; k < O; ++k)
                             if (k >= n) a.ystate_next[band * O + k] = st[b][k - n];
+                    }
+                }
+                if constexpr (EV) {
+                    if (evb) {   // the band's last row sits at t = n
+                        const double* rw = ev_rows + (long)(er1 - 1) * kRow;
+                        a.pgstate_next[2 * band] = rw[hz_fbev::kP];
+                        a.pgstate_next[2 * band + 1] = rw[hz_fbev::kG];
+                        continue;
                     }
                 }
                 // closed-form end state of the one-pole smoothers after n samples
@@ -565,6 +693,7 @@ static void build_record_any(int O, const double* b, const double* a, double* re
 }
 
 typedef void (*MixKernel)(const double*, MixArgs);
+typedef void (*MixKernelEv)(const double*, MixArgsEv);
 typedef void (*CarryKernel)(const double*, const double*, double*, int, int, long);
 
 template <int O, int PF, int NB>
@@ -602,6 +731,37 @@ static MixKernel pick_kernel(int O, int dist, int waves, int nb, int mode) {
     }
 }
 
+// the event form: one band per wave at every workgroup size
+template <int O, int PF>
+MixKernelEv pick_dist_ev(int dist, int mode) {
+    if (mode == MODE_SEGEND) return fb_mix_kernel<O, HZ_DIST_NONE, 1, MODE_SEGEND, PF, true>;
+    switch (dist) {
+    case HZ_DIST_SOFTCLIP: return fb_mix_kernel<O, HZ_DIST_SOFTCLIP, 1, MODE_MIX, PF, true>;
+    case HZ_DIST_SATURATE: return fb_mix_kernel<O, HZ_DIST_SATURATE, 1, MODE_MIX, PF, true>;
+    case HZ_DIST_LIMITER: return fb_mix_kernel<O, HZ_DIST_LIMITER, 1, MODE_MIX, PF, true>;
+    default: return fb_mix_kernel<O, HZ_DIST_NONE, 1, MODE_MIX, PF, true>;
+    }
+}
+
+template <int PF>
+MixKernelEv pick_order_ev(int O, int dist, int mode) {
+    switch (O) {
+    case 0: return pick_dist_ev<0, PF>(dist, mode);
+    case 1: return pick_dist_ev<1, PF>(dist, mode);
+    case 2: return pick_dist_ev<2, PF>(dist, mode);
+    case 3: return pick_dist_ev<3, PF>(dist, mode);
+    default: return pick_dist_ev<4, PF>(dist, mode);
+    }
+}
+
+static MixKernelEv pick_kernel_ev(int O, int dist, int waves, int mode) {
+    switch (waves) {
+    case 16: return pick_order_ev<2>(O, dist, mode);
+    case 8: return pick_order_ev<3>(O, dist, mode);
+    default: return pick_order_ev<5>(O, dist, mode);
+    }
+}
+
 static CarryKernel pick_carry(int O) {
     switch (O) {
     case 1: return fb_seg_carry_kernel<1>;
@@ -615,8 +775,9 @@ static CarryKernel pick_carry(int O) {
 
 namespace {
 
-int fb_groups(const hz_fb* h) {
-    const int per = h->waves * h->bands_per_wave;
+// workgroups over the bands; the event form runs one band per wave at the handle's wave count
+int fb_groups(const hz_fb* h, bool ev = false) {
+    const int per = h->waves * (ev ? 1 : h->bands_per_wave);
     return (h->N + per - 1) / per;
 }
 
@@ -676,8 +837,8 @@ int fb_upload(hz_fb* h) {
 }
 
 // chunk bound so the partial slab stays <= ~1 GiB
-long fb_max_chunk(const hz_fb* h) {
-    const long G = fb_groups(h);
+long fb_max_chunk(const hz_fb* h, bool ev = false) {
+    const long G = fb_groups(h, ev);
     long c = (1L << 27) / std::max(1L, G);  // doubles per row
     c = std::max<long>(kTile, (c / kTile) * kTile);
     return c;
@@ -735,26 +896,35 @@ void fb_mirror_sync_band(hz_fb* h, int l) {
     mirror_apply(h, l, (double)powl((long double)h->sp, (long double)d), (double)powl((long double)h->sg, (long double)d));
 }
 
-int fb_launch_general(hz_fb* h, const double* d_in, double* d_out, long n) {
+int fb_launch_general(hz_fb* h, const double* d_in, double* d_out, long n, const int* ev_off, const double* ev_rows) {
     if (n <= 0) return HZ_OK;
-    const int G = fb_groups(h);
+    const bool ev = ev_rows != nullptr;   // event form: the rows count from this call's sample 0, one launch
+    const int G = fb_groups(h, ev);
     const int O = h->order;
-    const long chunk = fb_max_chunk(h);
+    const long chunk = fb_max_chunk(h, ev);
+    if (ev && n > chunk) {
+        hz::set_error("fb_launch_general: an event piece of %ld samples exceeds one launch (%ld)", n, chunk);
+        return HZ_E_INVALID;
+    }
     const long n_pad_max = std::min<long>(((n + kTile - 1) / kTile) * kTile, chunk);
     const size_t need = (size_t)G * n_pad_max;
     HZ_TRY(h->d_partial.reserve(need));
     MixKernel kmix = pick_kernel(O, h->dist_id, h->waves, h->bands_per_wave, MODE_MIX);
     MixKernel kend = pick_kernel(O, h->dist_id, h->waves, h->bands_per_wave, MODE_SEGEND);
-    HZ_TRY(hz::allow_lds(h->device, (const void*)kmix, kLdsCeiling));
+    MixKernelEv kmix_ev = pick_kernel_ev(O, h->dist_id, h->waves, MODE_MIX);
+    MixKernelEv kend_ev = pick_kernel_ev(O, h->dist_id, h->waves, MODE_SEGEND);
     const size_t lds = lds_bytes(h->waves, true);
-    const size_t lds_end = lds_bytes(h->waves, false);
+    // (the event form's pre-pass steps pre[t] through the waves' LDS rows too)
+    const size_t lds_end = lds_bytes(h->waves, ev);
+    if (ev) HZ_TRY(hz::allow_lds(h->device, {(const void*)kmix_ev, (const void*)kend_ev}, kLdsCeiling));
+    else HZ_TRY(hz::allow_lds(h->device, (const void*)kmix, kLdsCeiling));
     for (long off = 0; off < n; off += chunk) {
         const long len = std::min(chunk, n - off);
         // time segments: enough workgroups to cover every CU at least once
         const hz::MixPlan mp = hz::mix_plan(G, len, kTile, h->target_groups);
         const long nseg = mp.nseg, seg_tiles = mp.seg_tiles;
         if (nseg > 1 && O > 0) HZ_TRY(h->d_seg.reserve((size_t)h->N * nseg * O));
-        MixArgs a;
+        MixArgsEv a;
         a.rec = h->d_rec;
         a.pin = h->d_pin;
         a.gin = h->d_gin;
@@ -779,6 +949,8 @@ int fb_launch_general(hz_fb* h, const double* d_in, double* d_out, long n) {
         a.sp_n = (double)powl((long double)h->sp, (long double)len);
         a.sg_n = (double)powl((long double)h->sg, (long double)len);
         a.dist_param = h->dist_param;
+        a.ev_off = ev_off;
+        a.ev_rows = ev_rows;
         hipEvent_t* e = nullptr;
         if (h->prof) {
             HZ_TRY(fb_prof_events(h, &e));
@@ -786,8 +958,12 @@ int fb_launch_general(hz_fb* h, const double* d_in, double* d_out, long n) {
         }
         if (nseg > 1 && O > 0) {
             // segment end states (zero-state), then the per-band carry over segments
-            hipLaunchKernelGGL(kend, dim3(G, (unsigned)(nseg - 1)), dim3(64 * h->waves), lds_end, h->stream,
-                               (const double*)h->d_rec, a);
+            if (ev)
+                hipLaunchKernelGGL(kend_ev, dim3(G, (unsigned)(nseg - 1)), dim3(64 * h->waves), lds_end, h->stream,
+                                   (const double*)h->d_rec, a);
+            else
+                hipLaunchKernelGGL(kend, dim3(G, (unsigned)(nseg - 1)), dim3(64 * h->waves), lds_end, h->stream,
+                                   (const double*)h->d_rec, (MixArgs)a);
             HZ_TRY_HIP(hipGetLastError());
             hipLaunchKernelGGL(pick_carry(O), dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream,
                                (const double*)h->d_rec, (const double*)h->d_ystate[h->scur], h->d_seg, h->N, (int)nseg,
@@ -795,8 +971,12 @@ int fb_launch_general(hz_fb* h, const double* d_in, double* d_out, long n) {
             HZ_TRY_HIP(hipGetLastError());
         }
         if (e) HZ_TRY_HIP(hipEventRecord(e[1], h->stream));
-        hipLaunchKernelGGL(kmix, dim3(G, (unsigned)nseg), dim3(64 * h->waves), lds, h->stream,
-                           (const double*)h->d_rec, a);
+        if (ev)
+            hipLaunchKernelGGL(kmix_ev, dim3(G, (unsigned)nseg), dim3(64 * h->waves), lds, h->stream,
+                               (const double*)h->d_rec, a);
+        else
+            hipLaunchKernelGGL(kmix, dim3(G, (unsigned)nseg), dim3(64 * h->waves), lds, h->stream,
+                               (const double*)h->d_rec, (MixArgs)a);
         HZ_TRY_HIP(hipGetLastError());
         if (e) HZ_TRY_HIP(hipEventRecord(e[2], h->stream));
         if (e) HZ_TRY_HIP(hipEventRecord(e[3], h->stream));
@@ -1208,6 +1388,163 @@ int hz_fb_process(hz_fb* h, const double* in, double* out, size_t n) {
     HZ_TRY(fb_launch(h, h->d_in, h->d_out, (long)n));
     HZ_TRY_HIP(hipMemcpyAsync(out, h->d_out, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
+    return HZ_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// the compiled rows of a piece -> device, through the handle's pinned staging
+int fb_ev_upload(hz_fb* h, const hz_fbev::Plan& P, const int** d_off, const double** d_rows) {
+    const size_t b_off = (P.seg_off.size() * sizeof(int) + 7) & ~(size_t)7, b_rows = P.rows.size() * sizeof(double);
+    const size_t bytes = b_off + b_rows;
+    if (!h->ev_up) HZ_TRY(h->ev_up.create(hipEventDisableTiming));
+    if (h->ev_up_pending) HZ_TRY_HIP(hipEventSynchronize(h->ev_up));   // staging buffer reuse
+    h->ev_up_pending = false;
+    if (bytes > h->h_ev.cap()) HZ_TRY(h->h_ev.reserve(std::max(bytes, 2 * h->h_ev.cap())));
+    if (bytes > h->d_ev.cap()) {
+        HZ_TRY_HIP(hipStreamSynchronize(h->stream));   // (an earlier piece's kernels read the old one)
+        HZ_TRY(h->d_ev.reserve(std::max(bytes, 2 * h->d_ev.cap())));
+    }
+    char* hs = h->h_ev;
+    std::memcpy(hs, P.seg_off.data(), P.seg_off.size() * sizeof(int));
+    std::memcpy(hs + b_off, P.rows.data(), b_rows);
+    HZ_TRY_HIP(hipMemcpyAsync(h->d_ev, hs, bytes, hipMemcpyHostToDevice, h->stream));
+    HZ_TRY_HIP(hipEventRecord(h->ev_up, h->stream));
+    h->ev_up_pending = true;
+    *d_off = (const int*)(const char*)h->d_ev;
+    *d_rows = (const double*)((const char*)h->d_ev + b_off);
+    return HZ_OK;
+}
+
+// One piece of an events call: len samples (within one launch) and the events whose times
+// at - t_base fall in [0, len].  What every target setter does first comes first -- the engines
+// that rest on constant targets disarm, streamed samples reach the smoothers, the mirror comes
+// current -- then the general engine's event form runs the piece, and the targets, the mirror and
+// the device smoothers end where the split sequence would leave them.
+int fb_events_piece(hz_fb* h, const double* d_in, double* d_out, long len, const hz_fb_event* ev, int nev,
+                    long t_base) {
+    hz_fbi::fb_rt_target_setter(h, hz_fbi::kAllBands);
+    h->setter_seq = h->rt.seq;
+    hz_fbi::fb_resp_setter(h);
+    fb_mirror_sync(h);
+    h->converged = false;
+    h->dirty_pin = h->dirty_gin = true;
+    HZ_TRY(fb_upload(h));
+    hz_fbev::Plan& P = h->ev_plan;
+    const int rc = hz_fbev::compile(ev, nev, t_base, len, h->N_total, h->band_begin, h->N, h->sp, h->sg,
+                                    h->pin.data(), h->gin.data(), h->pg_host.data(), &P);
+    if (rc != HZ_OK) {   // (validated by the caller: not reached)
+        hz::set_error("hz_fb_process_events: invalid event array");
+        return rc;
+    }
+    if (len > 0) {
+        h->spare_ok = len == 1;
+        h->last_path = HZ_FB_PATH_GENERAL;
+        HZ_TRY(fb_resp_materialize(h));
+        const int* d_off = nullptr;
+        const double* d_rows = nullptr;
+        if (!P.bands.empty()) HZ_TRY(fb_ev_upload(h, P, &d_off, &d_rows));   // (none: every event on another shard)
+        HZ_TRY(fb_launch_general(h, d_in, d_out, len, d_off, d_rows));
+        HZ_TRY(fb_resp_track(h, d_in, len, false));
+    }
+    if (P.bands.empty()) return HZ_OK;
+    for (int b : P.bands) {   // the band's last row: the targets staged for what follows, the end state
+        const double* rw = &P.rows[(size_t)(P.seg_off[b + 1] - 1) * hz_fbev::kRow];
+        h->pin[b] = rw[hz_fbev::kPin];
+        h->gin[b] = rw[hz_fbev::kGin];
+        h->pg_host[2 * (size_t)b] = rw[hz_fbev::kP];
+        h->pg_host[2 * (size_t)b + 1] = rw[hz_fbev::kG];
+        h->mirror_at[b] = h->mirror_clock;
+    }
+    hz_fbi::fb_rt_target_setter(h, hz_fbi::kAllBands);
+    h->dirty_pin = h->dirty_gin = true;
+    return HZ_OK;
+}
+
+int fb_events_check(hz_fb* h, size_t n, const hz_fb_event* ev, int nev, const char* who) {
+    int bad = -1;
+    const int rc = hz_fbev::validate(ev, nev, (long)n, h->N_total, &bad);
+    if (rc == HZ_E_RANGE)
+        hz::set_error("%s: event %d: band %d out of range [-1,%d)", who, bad, ev[bad].band, h->N_total);
+    else if (rc != HZ_OK && bad >= 0)
+        hz::set_error("%s: event %d {at %ld, kind %d}: kind must be HZ_FB_EV_BOOST / _MIX and at ascending in [0,%zu]",
+                      who, bad, ev[bad].at, ev[bad].kind, n);
+    else if (rc != HZ_OK)
+        hz::set_error("%s: invalid event array (nev %d)", who, nev);
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hz_fb_process_events_device(hz_fb* h, const double* d_in, double* d_out, size_t n, const hz_fb_event* ev,
+                                int nev) {
+    if (!h || (n > 0 && (!d_in || !d_out))) {
+        hz::set_error("hz_fb_process_events_device: null handle or buffer");
+        return HZ_E_INVALID;
+    }
+    hz_fbi::HandleLock lk(h);
+    HZ_TRY(fb_events_check(h, n, ev, nev, "hz_fb_process_events_device"));
+    if (nev == 0) return hz_fb_process_device(h, d_in, d_out, n);
+    long pos = 0;
+    if (n > 0 && h->rt.computed) {   // the cached sample first, as hz_fb_process_device: setters before
+        HZ_TRY_HIP(hipSetDevice(h->device));   // it change no sample already computed
+        double y0 = 0;
+        const int k = hz_fbi::fb_rt_resolve(h, &y0);
+        if (k < 0) return k;
+        double* pin0 = hz_fbi::fb_rt_cached_slot(h);
+        *pin0 = y0;
+        HZ_TRY_HIP(hipMemcpyAsync(d_out, pin0, sizeof(double), hipMemcpyHostToDevice, h->stream));
+        pos = 1;
+    }
+    HZ_TRY(fb_check(h));
+    const long N = (long)n, chunk = fb_max_chunk(h, true);
+    bool ran = false;
+    int i = 0;
+    while (i < nev) {
+        const long first = std::max(ev[i].at, pos);
+        if (first > pos) {   // the samples before the next event: the ordinary dispatch
+            HZ_TRY(fb_upload(h));
+            HZ_TRY(fb_launch(h, d_in + pos, d_out + pos, first - pos));
+            pos = first;
+        }
+        const long len = std::min(N - pos, chunk);
+        int j = i;   // (events at n ride with the call's last piece)
+        while (j < nev && (ev[j].at < pos + len || pos + len == N)) ++j;
+        HZ_TRY(fb_events_piece(h, d_in + pos, d_out + pos, len, ev + i, j - i, pos));
+        ran = ran || len > 0;
+        pos += len;
+        i = j;
+    }
+    if (pos < N) {   // (a call longer than one event launch: its rest has no events)
+        HZ_TRY(fb_upload(h));
+        HZ_TRY(fb_launch(h, d_in + pos, d_out + pos, N - pos));
+    }
+    if (ran) h->last_path = HZ_FB_PATH_GENERAL;
+    return HZ_OK;
+}
+
+int hz_fb_process_events(hz_fb* h, const double* in, double* out, size_t n, const hz_fb_event* ev, int nev) {
+    if (!h || (n > 0 && (!in || !out))) {
+        hz::set_error("hz_fb_process_events: null handle or buffer");
+        return HZ_E_INVALID;
+    }
+    hz_fbi::HandleLock lk(h);
+    HZ_TRY(fb_events_check(h, n, ev, nev, "hz_fb_process_events"));
+    if (nev == 0) return hz_fb_process(h, in, out, n);
+    if (n > 0) {
+        HZ_TRY(h->d_in.reserve(n));
+        HZ_TRY(h->d_out.reserve(n));
+        HZ_TRY_HIP(hipMemcpyAsync(h->d_in, in, sizeof(double) * n, hipMemcpyHostToDevice, h->stream));
+    }
+    HZ_TRY(hz_fb_process_events_device(h, h->d_in, h->d_out, n, ev, nev));
+    if (n > 0) {
+        HZ_TRY_HIP(hipMemcpyAsync(out, h->d_out, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+        HZ_TRY_HIP(hipStreamSynchronize(h->stream));
+    }
     return HZ_OK;
 }
 

@@ -16,6 +16,28 @@ from ._lib import HZ_DIST_NONE, HZ_DIST_SOFTCLIP, PD, check, dptr, load
 
 
 TV_COEFFS, TV_RESONANT = 0, 1   # HZ_FB_TV_*
+EV_BOOST, EV_MIX = 0, 1         # HZ_FB_EV_*
+
+# hz_fb_event {long at; int band; int kind; double value;}
+FB_EVENT = np.dtype([("at", np.int64), ("band", np.int32), ("kind", np.int32), ("value", np.float64)])
+
+
+def pack_events(events) -> np.ndarray:
+    """events -> hz_fb_event array: a sequence of (at, band, kind, value), four parallel arrays
+    (at, band, kind, value), or an array already of dtype FB_EVENT."""
+    if isinstance(events, np.ndarray) and events.dtype == FB_EVENT:
+        return np.ascontiguousarray(events)
+    if isinstance(events, tuple) and len(events) == 4 and all(np.ndim(e) == 1 for e in events):
+        cols = [np.asarray(e) for e in events]
+        if len({len(c) for c in cols}) != 1:
+            raise ValueError("process_events: the four event arrays differ in length")
+    else:
+        ev = list(events or ())
+        cols = [np.asarray([e[i] for e in ev]) for i in range(4)]
+    a = np.zeros(len(cols[0]), dtype=FB_EVENT)
+    for name, c in zip(("at", "band", "kind", "value"), cols):
+        a[name] = c
+    return a
 
 
 class Filterbank:
@@ -101,6 +123,25 @@ class Filterbank:
     def process_device(self, x_ptr: int, out_ptr: int, n: int):
         """Device pointers, asynchronous on the handle's stream."""
         check(self._lib.hz_fb_process_device(self._h, C.c_void_p(x_ptr), C.c_void_p(out_ptr), n))
+
+    def process_events(self, x, events) -> np.ndarray:
+        """process(x) with boost / mix setters inside the call (hz_fb_process_events): event
+        (at, band, kind, value) is boost(band, value) (EV_BOOST) or mix(band, value) (EV_MIX) made
+        before sample `at` is computed; band -1 is every band; `at` ascending in [0, len(x)].
+        `events`: a sequence of such tuples or four parallel arrays (pack_events)."""
+        xi = np.ascontiguousarray(x, dtype=np.float64)
+        ev = pack_events(events)
+        out = np.empty_like(xi)
+        check(self._lib.hz_fb_process_events(self._h, dptr(xi), dptr(out), len(xi),
+                                             C.c_void_p(ev.ctypes.data) if ev.size else None, ev.size))
+        return out
+
+    def process_events_device(self, x_ptr: int, out_ptr: int, n: int, events):
+        """Device pointers for the samples, asynchronous on the handle's stream; the events stay on
+        the host and are consumed before the call returns."""
+        ev = pack_events(events)
+        check(self._lib.hz_fb_process_events_device(self._h, C.c_void_p(x_ptr), C.c_void_p(out_ptr), n,
+                                                    C.c_void_p(ev.ctypes.data) if ev.size else None, ev.size))
 
     def process_tv(self, x, kind: int, stream, param: float = 0.0) -> np.ndarray:
         """Per-sample coefficient streams (hz_fb_process_tv): kind TV_COEFFS with stream

@@ -675,6 +675,53 @@ int hz_fb_process_tv(hz_fb* h, const double* in, double* out, size_t n, int kind
 int hz_fb_process_tv_device(hz_fb* h, const double* d_in, double* d_out, size_t n, int kind,
                             const double* d_stream, double param);
 
+/* ---- Filterbank with sample-accurate boost / mix events inside one block call ----
+ * The reference's MIDI instrument (tests/filterbank.cpp:217-252) turns every note-on and
+ * note-off into boost(n, v) and mix(n, v) while the audio loop runs.  An event
+ * {at, band, kind, value} is that setter call made before sample `at` is computed (the
+ * convention of hz_frz_event), so the call equals
+ *     n x { setters with at == t;  out[t] = F(in[t]);  F.tick(); }
+ * i.e. hz_fb_process on the pieces between distinct `at` values with hz_fb_boost / hz_fb_mix
+ * between them.
+ *   ordering  0 <= at <= n, non-decreasing through the array; events with equal `at` apply in
+ *             array order (the last one on a band and kind wins); at == n only stages the
+ *             target for the next call.
+ *   band      >= 0: one band by GLOBAL index (a shard ignores bands outside its range, as the
+ *             setters do); -1: every band of the handle -- open() is {at, -1, HZ_FB_EV_MIX, 1.0},
+ *             boost(vector of one value) its BOOST twin.
+ *   errors    band outside [-1, N_total): HZ_E_RANGE.  A bad kind, at > n, a descending at or
+ *             nev < 0: HZ_E_INVALID.  The whole array is validated first: on an error nothing
+ *             has been processed and no target has changed.
+ *   after     the staged targets, the host mirror and hz_fb_get_state are those of the split
+ *             sequence; any later call (hz_fb_process, hz_fb_process_tv, hz_fb_sample, another
+ *             events call) continues from there.
+ *   nev == 0  is hz_fb_process itself: same path, same bits.
+ *   engines   the first event disarms the converged (LTI), stationary and streaming engines
+ *             exactly as the setter would (they re-arm by their own rules in later calls).  The
+ *             samples before the first event go through the ordinary hz_fb_process dispatch;
+ *             from the first event's `at` on the call runs on the general engine's event form
+ *             (hz_filterbank.hip, fb_mix_kernel<.., EV>), and hz_fb_last_path reports
+ *             HZ_FB_PATH_GENERAL for a call that contained an event with at < n.  The event form
+ *             is built for one band per wave: a handle tuned to 2 or 4 bands per wave runs its
+ *             event samples with 1 band per wave at the same wave count.
+ *   others    a handle in per-sample mode is converted back as for any block call; distortion,
+ *             hz_fb_tune, hz_fb_set_target_groups, hz_fb_set_stream and hz_fb_profile apply as
+ *             for hz_fb_process.
+ * coefficients() inside a block is not an event: it breaks the carry scan and is what
+ * hz_fb_process_tv is for.  _device takes device pointers for the samples (asynchronous on the
+ * handle's stream); `ev` stays on the host and is consumed before the call returns. */
+#define HZ_FB_EV_BOOST 0 /* boost(band, value), filterbank.h:85-88  */
+#define HZ_FB_EV_MIX 1   /* mix(band, value),   filterbank.h:99-102 */
+typedef struct {
+    long at;
+    int band;
+    int kind;
+    double value;
+} hz_fb_event;
+int hz_fb_process_events(hz_fb* h, const double* in, double* out, size_t n, const hz_fb_event* ev, int nev);
+int hz_fb_process_events_device(hz_fb* h, const double* d_in, double* d_out, size_t n, const hz_fb_event* ev,
+                                int nev);
+
 /* ---- heterodyne bank chain of tests/harmbank.cpp:77-101, fused over `channels` ----
  * Per sample x:  y = limiter(dry x + gain mixdown(demodulators(synthesis(),
  *     smoothbank(latchbank(&rmsbank, slidebank(modulators(x, analysis())))))))

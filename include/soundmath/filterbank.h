@@ -52,6 +52,27 @@ public:
         detail::check(hz_fb_set_distortion(h_.get(), dist_id, param), "Filterbank::process");
         detail::check(hz_fb_process(h_.get(), in, out, n), "Filterbank::process");
     }
+    // (new) n x { setters with at == t; out[t] = operator()(in[t]); tick(); } -- boost / mix calls at
+    // sample positions inside one block (hz_fb_process_events; band -1: every band).  The MIDI
+    // thread of tests/filterbank.cpp:231-245 queues events instead of calling the setters, with `at`
+    // the sample of the current block at which the message arrived:
+    //     if (velocity && status != note_off)
+    //         for (int j = 0; j < courses; j++) {
+    //             ev.push_back({at, courses * index + j, HZ_FB_EV_BOOST, 1});
+    //             ev.push_back({at, courses * index + j, HZ_FB_EV_MIX, gains[courses * index + j]});
+    //         }
+    //     else
+    //         for (int j = 0; j < courses; j++) {
+    //             ev.push_back({at, courses * index + j, HZ_FB_EV_BOOST, 0});
+    //             ev.push_back({at, courses * index + j, HZ_FB_EV_MIX, 0});
+    //         }
+    // and the audio callback makes one call per block: F.process(in, out, BSIZE, ev.data(), ev.size()).
+    void process(const T* in, T* out, std::size_t n, const hz_fb_event* ev, int nev, int dist_id = HZ_DIST_NONE,
+                 double param = -1.0) {
+        if (param < 0.0) param = HZ_DIST_DEFAULT_PARAM(dist_id);
+        detail::check(hz_fb_set_distortion(h_.get(), dist_id, param), "Filterbank::process");
+        detail::check(hz_fb_process_events(h_.get(), in, out, n, ev, nev), "Filterbank::process");
+    }
     // n x { coefficients(b, row t) for every band b; out[t] = operator()(in[t]); tick(); } --
     // the Subtractive ALLINONE / ONEPERVOICE pattern (src/subtractive.h:215-228, 300-317) as one
     // call.  coeffs: [n][2*order+1][N] (forward then back, band-minor).  The last row stays set.

@@ -19,7 +19,10 @@
 // per-chunk exp seed and a per-sample factor (x's float rounding changes the term by
 // < 2.5e-8 a_i).  The sum is kept in double (the reference rounds it to float after every
 // mode; that accumulation differs by ~1e-7 relative, see tests).  The float counter
-// saturates at 2^24 (phase++ stops incrementing), as in the reference.
+// saturates at 2^24 (phase++ stops incrementing) and the reference's sample is a function of
+// the counter alone, so its output is constant from there on: samples whose counter is 2^24 are
+// the bank's one value at 2^24 (stuck_sum, worked out at creation), not the chunk's stepped
+// decay, which would keep falling inside a chunk and jump back at the next seed.
 #include <algorithm>
 #include <cmath>
 #include <complex>
@@ -39,7 +42,6 @@ using namespace hz::mix;   // kWaves, kMaxPerWave, kPad, cmul and the end-of-til
 
 constexpr int kL = 16;
 constexpr int kTile = tile_len(kL);
-constexpr double kPiM = 3.141592653589793115997963468544185161590576171875;  // M_PI (double)
 
 // per-mode record: a, W1 (2), T1[16] (32), T2[4] (8), WT (2), f, d, |w|  (48 doubles)
 struct BRec {
@@ -76,9 +78,12 @@ __device__ __forceinline__ float div_sr(float x) {
 // p >= 0: 2 PI p = 2 pi (p + p e) with e = PI / pi - 1, so with k = floor(p), r = p - k
 // (exact) the value is sin(2 pi (r + p e)).  r is folded into [-1/4, 1/4] by exact float
 // reflections (tracking the sign of the p e term), then an odd degree-11 polynomial in r
-// (|error| < 1.4e-11) -- far below the float rounding that follows.
-__device__ __forceinline__ double sin2pi_ref(float p) {
-    constexpr double kE = 3.14159265359 / kPiM - 1.0;
+// (|error| < 1.4e-11) -- far below the float rounding that follows.  e is a literal: PI here is
+// the double nearest 3.14159265359, and PI / pi - 1 worked out from 50 digits; the quotient
+// formed in double (3.14159265359 / M_PI - 1.0 = 6.5947e-14) keeps three digits of it, which at
+// p = 5.6e6 (16 kHz at the stuck counter) is 4.7e-9 in the sine.
+__host__ __device__ __forceinline__ double sin2pi_ref(float p) {
+    constexpr double kE = 6.58338396844303045e-14;
     const float k = floorf(p);
     float u = p - k;                      // [0, 1), exact
     u = u >= 0.5f ? u - 1.0f : u;         // [-1/2, 1/2), exact
@@ -99,9 +104,34 @@ __device__ __forceinline__ double sin2pi_ref(float p) {
 }
 
 // float phase counter after t increments from n0 (saturates at 2^24)
+constexpr double kStuck = 16777216.0;   // 2^24: float phase++ no longer moves the counter
 __device__ __forceinline__ float phase_f(double n0, long t) {
     const double v = n0 + (double)t;
-    return (float)(v < 16777216.0 ? v : 16777216.0);
+    return (float)(v < kStuck ? v : kStuck);
+}
+
+// The bank's one sample at the stuck counter: the float model at 2^24 itself, no chunk seed and
+// no stepping, modes summed in index order in double.  The reference's sample is a function of
+// the counter alone, so every sample at 2^24 -- the one that reaches it, the rest of its chunk,
+// later chunks, later calls -- is this value; it is worked out once, on the host (rec: the float
+// coefficients as doubles).
+double stuck_sum(const double* rec, int M) {
+    double s = 0.0;
+    for (int i = 0; i < M; ++i) {
+        const double* rr = rec + (size_t)i * BRec::SIZE;
+        const float fq = (float)rr[BRec::F], dq = (float)rr[BRec::D], aq = (float)rr[BRec::AMP];
+        const float ph = (float)kStuck;
+        const float x = -dq * ph / 48000.0f, p = fq * ph / 48000.0f;   // IEEE divide = div_sr
+        s = std::fma((double)aq * std::exp((double)x), (double)(float)sin2pi_ref(p), s);
+    }
+    return s;
+}
+
+// samples [t_s, n) of a call are at the stuck counter
+template <typename OutT>
+__global__ __launch_bounds__(256) void bowl_stuck_fill_kernel(OutT* __restrict__ out, long t_s, long n, double v) {
+    const long t = t_s + (long)blockIdx.x * 256 + threadIdx.x;
+    if (t < n) out[t] = (OutT)v;
 }
 
 __global__ __launch_bounds__(64 * kWaves) void bowl_mix_kernel(const double* __restrict__ rec, BowlArgs a) {
@@ -247,6 +277,8 @@ struct ChainArgs {
     const double* rstep;   // [M] E^{-d/SR} (BRec::R)
     int M;
     double n0;
+    float stuck;           // the bank's sample at the stuck counter (stuck_sum), from sample
+    long t_stuck;          // t_stuck of the block on (n when the block ends below 2^24)
     long n;
     float* buf;            // the fill buffer [n]
     hz_chain::DlyBlock d;
@@ -331,7 +363,8 @@ __global__ __launch_bounds__(kChainThreads) void bowl_dly_chain_kernel(ChainArgs
         double v = wsum[0][tid];
 #pragma unroll
         for (int w = 1; w < kW; ++w) v += wsum[w][tid];
-        const float x = (float)v;
+        // at the stuck counter the sample is the bank's one stuck value, not the stepped sum
+        const float x = t0 + tid >= a.t_stuck ? a.stuck : (float)v;
         xs[tid] = x;
         if (t0 + tid < a.n) a.buf[t0 + tid] = x;
     }
@@ -409,6 +442,7 @@ struct hz_bowl {
     hz::Stream stream;
     int M = 0, device = 0, is_float = 0;
     double n0 = 0;  // phase counter (T) at the next call
+    double stuck = 0;   // (float Bowls) the sample at the stuck counter 2^24 (stuck_sum)
     hz::DevBuf<double> d_rec, d_partial;
     hz::DevBuf<char> d_chain;   // (float Bowls) [M] float4 {f, d, a, 0} then [M] double decay steps
     hz::DevBuf<char> d_out;     // doubles or floats (bytes)
@@ -480,9 +514,22 @@ int bowl_launch(hz_bowl* h, void* d_dst, long n, int out_kind) {
     else
         slab_reduce(h->stream, (const double*)h->d_partial, n_pad, G, n, SlabStore<double>{(double*)d_dst});
     HZ_TRY_HIP(hipGetLastError());
+    // T = float: the samples from the one that reaches 2^24 on are the bank's stuck value (the
+    // kernel's stepped decay would go on falling inside a chunk and jump back at the next seed)
+    if (h->is_float && h->n0 + (double)n > kStuck) {
+        const long t_s = (long)std::max(0.0, kStuck - h->n0);
+        const dim3 grid((unsigned)((n - t_s + 255) / 256));
+        if (out_kind == 0)
+            hipLaunchKernelGGL(bowl_stuck_fill_kernel<float>, grid, dim3(256), 0, h->stream, (float*)d_dst, t_s, n,
+                               h->stuck);
+        else
+            hipLaunchKernelGGL(bowl_stuck_fill_kernel<double>, grid, dim3(256), 0, h->stream, (double*)d_dst, t_s,
+                               n, h->stuck);
+        HZ_TRY_HIP(hipGetLastError());
+    }
     // phase counter: T = double counts exactly; T = float saturates at 2^24
     h->n0 += (double)n;
-    if (h->is_float && h->n0 > 16777216.0) h->n0 = 16777216.0;
+    if (h->is_float && h->n0 > kStuck) h->n0 = kStuck;
     h->launches += h->prof ? 1 : 0;
     return HZ_OK;
 }
@@ -491,7 +538,7 @@ int bowl_launch(hz_bowl* h, void* d_dst, long n, int out_kind) {
 void bowl_settle(hz_bowl* h) {
     if (h->la_pos < h->la_n) {
         h->n0 = h->n0_snap + (double)h->la_pos;
-        if (h->is_float && h->n0 > 16777216.0) h->n0 = 16777216.0;
+        if (h->is_float && h->n0 > kStuck) h->n0 = kStuck;
     }
     h->la_n = h->la_pos = 0;
 }
@@ -554,6 +601,7 @@ int hz_bowl_create(int overtones, const double* f, const double* a, const double
         delete h;
         return HZ_E_ALLOC;
     }
+    if (h->is_float) h->stuck = stuck_sum(rec.data(), overtones);
     if (h->is_float) {   // the fused block's compact mode table (hz_bowl_fill_delaybank)
         std::vector<float> fda((size_t)overtones * 4, 0.0f);
         std::vector<double> rs((size_t)overtones);
@@ -697,6 +745,8 @@ int hz_bowl_fill_delaybank(hz_bowl* h, float* d_buf, hz_dly* bank, void* d_out, 
     a.rstep = (const double*)((const char*)h->d_chain + sizeof(float4) * h->M);
     a.M = h->M;
     a.n0 = h->n0;
+    a.stuck = (float)h->stuck;
+    a.t_stuck = (long)std::min((double)n, std::max(0.0, kStuck - h->n0));
     a.n = n;
     a.buf = d_buf;
     a.d = d;
@@ -707,7 +757,7 @@ int hz_bowl_fill_delaybank(hz_bowl* h, float* d_buf, hz_dly* bank, void* d_out, 
     HZ_TRY_HIP(hipGetLastError());
     if (e) HZ_TRY_HIP(hipEventRecord(e[1], h->stream));
     h->n0 += (double)n;
-    if (h->n0 > 16777216.0) h->n0 = 16777216.0;
+    if (h->n0 > kStuck) h->n0 = kStuck;
     h->launches += h->prof ? 1 : 0;
     hz_chain::dly_block_end(bank, n);
     return HZ_OK;

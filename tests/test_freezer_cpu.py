@@ -3,105 +3,12 @@ independent numpy restatement of src/fourier.h:236-562 (FFrame, IFrame, DFrame, 
 
 Parity status: the reference holds no fixtures for Freezer; these checks pin the
 restatement (the dry Delay path exactly, the frozen path against a second model to 1e-12)."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
+from freezer_model import PyFreezer
 from huygens_amd._lib import header_symbols
 from oracle_frz import OracleFreezer, libc_srand
-
-PI = 3.14159265359
-_libc = C.CDLL(None)
-
-
-def halfhann(p):
-    return np.sqrt(0.5 * (1 - np.cos(2 * PI * p)))
-
-
-class PyFreezer:
-    """numpy restatement, per sample (small N only); rand() from libc like the reference."""
-
-    def __init__(self, N, laps, width):
-        width, laps = max(width, 1.0), max(laps, 2)
-        self.N, self.stride = N, N // laps
-        self.M = int(width * laps) + 1
-        self.size = self.M * self.stride
-        M = self.M
-        self.data = np.zeros((M, N), complex)
-        self.norms = np.zeros((M, N))
-        self.phases = np.zeros((M, N))
-        self.dn = np.zeros((M, N))
-        self.dp = np.zeros((M, N))
-        self.idata = np.zeros((M, N), complex)
-        self.iqueue = [0] * M
-        self.iindex = self.origin = self.readhead = self.excluded = 0
-        self.frozen = False
-        self.din = np.zeros(N + 1)
-        self.dorigin = 0
-        self.win = halfhann(np.arange(N) / N)
-
-    def write(self, x):
-        for i in range(self.M):
-            spot = (self.origin - i * self.stride) % self.size
-            if spot < self.N:
-                self.data[i, spot] = complex(self.win[spot] * x, self.win[spot] * 0.0)
-            if spot == 0:
-                j = (i - 1) % self.M
-                X = np.fft.fft(self.data[j])
-                self.norms[j] = X.real ** 2 + X.imag ** 2
-                self.phases[j] = np.arctan2(X.imag, X.real)
-        self.origin = (self.origin + 1) % self.size
-
-    def freeze(self):
-        if not self.frozen:
-            self.excluded = self.origin // self.stride
-            for i in range(1, self.M - 1):
-                d = (self.excluded + i) % self.M
-                s = (d + 1) % self.M
-                self.dn[d] = self.norms[s]
-                self.dp[d] = self.phases[s] - self.phases[d]
-        self.readhead = 0
-        self.frozen = True
-
-    def unfreeze(self):
-        self.frozen = False
-
-    def sample(self, x):
-        self.write(x)
-        out = 0.0
-        if self.frozen:
-            for i in range(self.M):
-                spot = (self.readhead - i * self.stride) % self.size
-                if spot < self.N:
-                    out += self.idata[self.iqueue[i], spot].real * self.win[spot]
-                if spot == 0:
-                    nxt = _libc.rand() % (self.M - 2)
-                    if nxt >= self.excluded:
-                        nxt += 2
-                    self.iindex = (self.iindex + 1) % self.M
-                    self.iqueue[self.iindex] = nxt
-                    voc = np.fmod(self.dp[nxt], 2 * PI)
-                    r = np.sqrt(self.dn[nxt])
-                    self.idata[nxt] = np.fft.ifft(r * np.cos(voc) + 1j * r * np.sin(voc)) * self.N
-            self.readhead = (self.readhead + 1) % self.size
-            out /= self.N
-        else:
-            o = self.dorigin
-            self.din[o] = x
-            out = self.din[(o + 1) % (self.N + 1)]
-        self.dorigin = (self.dorigin + 1) % (self.N + 1)
-        return out
-
-    def process(self, x, events=()):
-        ev = list(events)
-        y, k = np.zeros(len(x)), 0
-        for i, xi in enumerate(x):
-            while k < len(ev) and ev[k][0] == i:
-                self.freeze() if ev[k][1] else self.unfreeze()
-                k += 1
-            y[i] = self.sample(xi)
-        return y
 
 
 def test_dry_path_is_an_n_sample_delay():

@@ -165,20 +165,18 @@ __device__ __forceinline__ void real_window_fwd(hz2k::Lds& s, Load load, const d
                                                 bool stamps = false) {
     const int t = threadIdx.x;
     if (stamps) HZ_DIAG_AT(0, 0);
-    // every global load of the thread (data, pass twiddles, split twiddles) before the first use
+    // every global load of the thread (data, pass twiddles, split twiddles) before the first use:
+    // load requests pair i = samples 2n, 2n + 1 (n = t + 256 i) into vr[i], vi[i]
     double vr[kPT], vi[kPT];
-#pragma unroll
-    for (int i = 0; i < kPT; ++i) {
-        const int n = t + i * kThreads;
-        const double2 v = load(2 * n);   // samples 2n, 2n + 1
-        vr[i] = v.x;
-        vi[i] = v.y;
-    }
+    load(vr, vi);
     hz2k::FwdTw ft;
     ft.load(twf);
     double2 w[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) w[i] = twf[(hz2k::kTwSlots + i) * kThreads + t];
+    // (straight-line loads: without this the scheduler starts the first pass on the data between the
+    // twiddle loads, behind a wait, to save registers)
+    __builtin_amdgcn_sched_barrier(0);
 #ifdef HZ_DIAG_STAMPS
     if (stamps) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -216,12 +214,16 @@ __global__ __launch_bounds__(kThreads) void resp_hspec_kernel(const double* __re
     const long p0 = (long)blockIdx.x * kP;
     real_window_fwd<kStPlain>(   // setup, once per coefficient change: plain
         s,
-        [&](int m) {
+        [&](double (&vr)[kPT], double (&vi)[kPT]) {
             auto g = [&](int k) { return (k < kP && p0 + k < K) ? h[p0 + k] * (1.0 / kF) : 0.0; };
-            return make_double2(g(m), g(m + 1));
+#pragma unroll
+            for (int i = 0; i < kPT; ++i) {
+                const int m = 2 * ((int)threadIdx.x + i * kThreads);
+                vr[i] = g(m);
+                vi[i] = g(m + 1);
+            }
         },
-        twf,
-        H + (long)blockIdx.x * kH, Hn + blockIdx.x);
+        twf, H + (long)blockIdx.x * kH, Hn + blockIdx.x);
 }
 
 struct RespArgs {
@@ -259,6 +261,55 @@ __device__ __forceinline__ double resp_u(const RespArgs& a, long m) {
     return m < a.off + a.n_out ? a.x[m] : 0.0;
 }
 
+// The loads of window W_j (m0 = jP), real_window_fwd's Load.  K and off are multiples of P (a
+// shard's off is, unless its range is empty), so each half of the window -- a thread's pairs i < 4
+// or i >= 4 -- lies wholly in hist or wholly at or after sample K: a base pointer and a valid
+// length per half, wave-uniform, in a buffer descriptor each, and a thread's eight 16-byte loads
+// go out back to back with no per-pair branch.  (Per pair, three exec-masked outcomes -- hist, x,
+// resp_u -- gave the history loads a vmcnt(0) each and, in every window, the first pass behind a
+// wait for the data and in front of 13 of the 14 twiddle loads: DESIGN.md 3.6, profiles/fwd_hist.)
+// The range check is per dword: samples past the call's end read as zeros, an odd length's last
+// pair as (x, 0).  A buffer load needs 4-byte alignment only, so buffers that are only 8-byte
+// aligned take the same loads.
+struct WindowLoad {
+    const RespArgs& a;
+    long m0;
+    __device__ __forceinline__ void operator()(double (&vr)[kPT], double (&vi)[kPT]) const {
+        const int t = threadIdx.x;
+        if (((a.K | a.off) & (kP - 1)) != 0) {   // halves may straddle: per pair
+            const bool al = ((reinterpret_cast<uintptr_t>(a.hist) | reinterpret_cast<uintptr_t>(a.x)) & 15) == 0;
+#pragma unroll
+            for (int i = 0; i < kPT; ++i) {
+                const int mm = 2 * (t + i * kThreads);
+                const long m = m0 + mm + a.off;
+                double2 v;
+                if (al && m + 1 < a.K) v = *reinterpret_cast<const double2*>(a.hist + m);
+                else if (al && m >= a.K && m + 1 - a.K < a.off + a.n_out) v = *reinterpret_cast<const double2*>(a.x + (m - a.K));
+                else v = make_double2(resp_u(a, m0 + mm), resp_u(a, m0 + mm + 1));
+                vr[i] = v.x;
+                vi[i] = v.y;
+            }
+            return;
+        }
+        __amdgpu_buffer_rsrc_t rs[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const long mh = m0 + a.off + h * kP;
+            const long left = a.off + a.n_out - (mh - a.K);   // valid samples from mh on, at or after K
+            const double* bp = mh < a.K ? a.hist + mh : a.x + (mh - a.K);
+            const int vl = mh < a.K ? kP : (int)(left <= 0 ? 0 : left >= kP ? kP : left);
+            rs[h] = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(bp), 0, 8 * vl, 0x00020000);
+        }
+#pragma unroll
+        for (int i = 0; i < kPT; ++i) {
+            const double2 v = __builtin_bit_cast(
+                double2, __builtin_amdgcn_raw_buffer_load_b128(rs[i / 4], 16 * (t + (i & 3) * kThreads), 0, 0));
+            vr[i] = v.x;
+            vi[i] = v.y;
+        }
+    }
+};
+
 // The inverse kernel carries the band-state pass (hz_fb_state.h) as extra workgroups past its own
 // (SO = the bank's order, 0: none): a CU holds one of each (<= 256 registers per wave, LDS the
 // larger of the two), so the latency-bound inverse transforms run beside the state pass.
@@ -288,22 +339,8 @@ __global__ __launch_bounds__(kThreads) void resp_fwd_kernel(RespArgs a, hz_modal
         HZ_DIAG_AT(0, 3);
         return;
     }
-    hz2k::Lds& s = u.fft;
-    const long m0 = (long)blockIdx.x * kP;
-    // the pair (m, m + 1), m even, lies in one of hist / x (K and off are even): one 16-byte load
-    // when that buffer is 16-byte aligned and the pair is inside the call
-    const bool al = ((reinterpret_cast<uintptr_t>(a.hist) | reinterpret_cast<uintptr_t>(a.x)) & 15) == 0;
-    real_window_fwd<kStZ>(
-        s,
-        [&](int mm) {
-            const long m = m0 + mm + a.off;
-            if (al) {
-                if (m + 1 < a.K) return *reinterpret_cast<const double2*>(a.hist + m);
-                if (m >= a.K && m + 1 - a.K < a.off + a.n_out) return *reinterpret_cast<const double2*>(a.x + (m - a.K));
-            }
-            return make_double2(resp_u(a, m0 + mm), resp_u(a, m0 + mm + 1));
-        },
-        a.twf, a.Z + (long)blockIdx.x * kH, a.Zn + blockIdx.x, true);
+    real_window_fwd<kStZ>(u.fft, WindowLoad{a, (long)blockIdx.x * kP}, a.twf, a.Z + (long)blockIdx.x * kH,
+                          a.Zn + blockIdx.x, true);
 }
 
 // (the MAC launch: hz_fb_mac.h)
@@ -1093,15 +1130,26 @@ int fb_launch_resp(hz_fb* h, const double* d_in, double* d_out, long n) {
                         for (int j = 0; j < 3; ++j) ph[j] += (hv[k][i][j + 1] - hv[k][i][j]) * 0.01;
                     }
                 }
-                if (k == 0 && nm1 > hz_modal::kPhase1) {   // phase-1 residues vs the exceptional bands' partials
-                    double e1 = 0, ex = 0;
-                    for (int i = nz; i < tot[0]; ++i) {
-                        const double e = (hv[0][i][3] - t0) * 0.01;
-                        if (i < nz + hz_modal::kPhase1) e1 = std::max(e1, e);
-                        else ex = std::max(ex, e);
+                if (k == 0) {   // the forward launch by class of workgroup: where its windows' samples lie, the modal phases
+                    static const char* const kClass[5] = {"history windows", "straddling window", "call windows",
+                                                          "phase-1 workgroups", "exceptional partials"};
+                    struct {
+                        int cnt = 0;
+                        double first = 1e30, last = 0, ph[3] = {0, 0, 0};
+                    } c[5];
+                    for (int i = 0; i < tot[0]; ++i) {
+                        const long m = off + (long)i * kP;   // the window's first sample in [hist | x]
+                        const int cl = i >= nz ? (i < nz + md.n1 ? 3 : 4) : m + kF <= K ? 0 : m < K ? 1 : 2;
+                        ++c[cl].cnt;
+                        c[cl].first = std::min(c[cl].first, (hv[0][i][0] - t0) * 0.01);
+                        c[cl].last = std::max(c[cl].last, (hv[0][i][3] - t0) * 0.01);
+                        for (int j = 0; j < 3; ++j) c[cl].ph[j] += (hv[0][i][j + 1] - hv[0][i][j]) * 0.01;
                     }
-                    std::fprintf(stderr, "[fwd stamps] phase-1 workgroups (%d) last end %.2f us, exceptional partials (%d) last end %.2f us\n",
-                                 hz_modal::kPhase1, e1, nm1 - hz_modal::kPhase1, ex);
+                    for (int cl = 0; cl < 5; ++cl)
+                        if (c[cl].cnt)
+                            std::fprintf(stderr, "[fwd stamps] %-20s %4d: first start %.2f us, mean operands %.2f us, compute %.2f us, "
+                                         "stores %.2f us, last end %.2f us\n", kClass[cl], c[cl].cnt, c[cl].first,
+                                         c[cl].ph[0] / c[cl].cnt, c[cl].ph[1] / c[cl].cnt, c[cl].ph[2] / c[cl].cnt, c[cl].last);
                 }
                 std::fprintf(stderr, "[%s stamps] %d workgroups: mean operands %.2f us, compute %.2f us, stores %.2f us; "
                              "starts up to %.2f us, last end %.2f us; %d modal workgroups, last end %.2f us\n",

@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstring>
 #include <mutex>
+#include <optional>
 #include <vector>
 
 #include "hz_common.h"
@@ -65,8 +66,8 @@ using hz::mix::lane_d;   // a lane's double by v_readlane
 // handle (the opaque hz_fb of include/huygens_hip.h)
 // ---------------------------------------------------------------------------
 struct hz_fb {
-    // entry points that touch the staged parameters or the state hold it (setters may come from
-    // another thread while samples run: tests/filterbank.cpp:217-252 vs 200-210)
+    // the sample-path and guarded entry points hold it (the table above hz_fbi::Entry; setters may
+    // come from another thread while samples run: tests/filterbank.cpp:217-252 vs 200-210)
     std::recursive_mutex mu;
     // setters waiting for `mu`: a per-sample call lets them in first (a thread calling operator()
     // in a tight loop would otherwise re-take the lock before a waiting setter is scheduled)
@@ -310,23 +311,20 @@ inline void cpu_relax() { __builtin_ia32_pause(); }
 // scheduler wake-up (5-10 us) per hand-off, a quarter of a sample period at 48 kHz
 constexpr int kSpinSetter = 1 << 16;    // ~ a few ms of pause instructions
 constexpr int kSpinSample = 1 << 20;
+inline void spin_lock(hz_fb* h, int spins) {
+    for (int spin = 0; !h->mu.try_lock(); cpu_relax())
+        if (++spin == spins) return h->mu.lock();
+}
 
-// the hold of a setter or any other entry point but operator() / tick() (SampleLock), announced
-// from before it locks until after it unlocks, so a per-sample call neither takes the lock ahead
-// of it (an audio thread spinning on the lock would otherwise starve a blocked waiter) nor blocks
+// the hold of a setter or any other guarded entry point (the table above Entry), announced from
+// before it locks until after it unlocks, so a per-sample call neither takes the lock ahead of it
+// (an audio thread spinning on the lock would otherwise starve a blocked waiter) nor blocks
 // behind it (hz_fb::setter_wait); it spins for the lock while a sample is being served
 struct HandleLock {
     hz_fb* h;
     explicit HandleLock(hz_fb* h_) : h(h_) {
         h->setter_wait.fetch_add(1);
-        int spin = 0;
-        while (!h->mu.try_lock()) {
-            if (++spin == kSpinSetter) {
-                h->mu.lock();
-                break;
-            }
-            cpu_relax();
-        }
+        spin_lock(h, kSpinSetter);
     }
     ~HandleLock() {
         h->mu.unlock();
@@ -351,14 +349,7 @@ struct SampleLock {
                 cpu_relax();
             }
         }
-        int spin = 0;
-        while (!h->mu.try_lock()) {
-            if (++spin == kSpinSample) {
-                h->mu.lock();
-                break;
-            }
-            cpu_relax();
-        }
+        spin_lock(h, kSpinSample);
     }
     ~SampleLock() { h->mu.unlock(); }
 };
@@ -375,7 +366,19 @@ void fb_rt_target_setter(hz_fb* h, int l);
 // (device pointers; n within one launch)
 int fb_launch_general(hz_fb* h, const double* d_in, double* d_out, long n, const int* ev_off = nullptr,
                       const double* ev_rows = nullptr);
-int fb_upload_staged(hz_fb* h);              // staged setters -> device
+// staged setters -> device; coefficients false: targets only, the coefficient records and
+// dirty_coef stay as they are (a coefficient-stream call reads neither)
+int fb_upload(hz_fb* h, bool coefficients = true);
+// a launch or tick rotation wrote the other state and x-history buffers: they are current now
+inline void fb_advance(hz_fb* h, long len) {
+    h->scur ^= 1;
+    h->xcur ^= 1;
+    fb_mirror_advance(h, len);
+}
+// the start of a block call: the cached sample of an operator() without tick() first (fb_rt_resolve;
+// to host memory, or through the pinned slot and the handle's stream to device memory), the state
+// back from the per-sample engine either way; -> samples consumed (0 or 1; out0 null: 0) or a code
+int fb_block_begin(hz_fb* h, double* out0, bool out_is_device);
 int fb_tv_materialize(hz_fb* h);             // pending stream row -> F/B (hz_fb_tv.hip)
 // hz_fb_lti.hip
 int fb_lti_geom(const hz_fb* h, long n);  // LTI geometry for a call of n samples
@@ -434,5 +437,45 @@ int fb_rt_stop(hz_fb* h);    // the resident kernel leaves (stream-ordered), pen
 // first (re-mixed with the block's distortion) and ticks; -> samples consumed (0 or 1)
 int fb_rt_resolve(hz_fb* h, double* y0);
 double* fb_rt_cached_slot(hz_fb* h);   // pinned host double for an async copy of that sample
+
+// Every extern "C" hz_fb_* function by what it holds (tests/test_fb_entry_points_cpu.py compares).
+// Guarded is whatever calls fb_rt_stop, fb_upload, fb_resp_materialize, fb_tv_materialize or
+// fb_tick_rotate, or touches F, B, pin, gin, pg_host, dirty_*, tv_pending, converged, resp.armed /
+// run / h_valid / over_valid / mode / shard_rank / shard_world or the stream.  The lock-free ones
+// are scalar tuning and snapshots: HandleLock announces a setter, SampleLock yields to that for up
+// to 20 us, and a monitoring thread must not stall the audio thread (resp.shard_zero counts as
+// tuning: one scalar, read only when a time-sharded call launches).
+//   sample path (SampleLock): hz_fb_sample hz_fb_sample_many hz_fb_sample_tick
+//   guarded, host staging only (HandleLock): hz_fb_coefficients hz_fb_boost hz_fb_boost_all hz_fb_mix
+//     hz_fb_mix_all hz_fb_open hz_fb_set_distortion hz_fb_setter_seq hz_fb_sample_info
+//     hz_fb_set_time_shard hz_fb_arm_time_shard
+//   guarded, device work (Entry; * = state_back false: fb_block_begin brings the state back, or
+//     the call leaves it with the per-sample engine): hz_fb_process* hz_fb_process_device*
+//     hz_fb_process_events* hz_fb_process_events_device* hz_fb_process_tv* hz_fb_process_tv_device*
+//     hz_fb_stationary_ready* hz_fb_get_response* hz_fb_set_response hz_fb_set_bank_response
+//     hz_fb_set_stream hz_fb_synchronize hz_fb_get_state hz_fb_set_state hz_fb_tick hz_fb_profile
+//     hz_fb_profile_read
+//   lock-free: hz_fb_info hz_fb_state_size hz_fb_get_stream hz_fb_tune hz_fb_set_target_groups
+//     hz_fb_set_path hz_fb_last_path hz_fb_lti_last_chunk hz_fb_lti_plan hz_fb_tune_lti
+//     hz_fb_tune_stream hz_fb_stream_info hz_fb_set_time_shard_fill hz_fb_tune_response_engine
+//     hz_fb_tune_modal hz_fb_modal_info hz_fb_response_engine hz_fb_tune_response
+//     hz_fb_time_shard_info hz_fb_response_info
+//   lifecycle (no other thread has the handle): hz_fb_create_shard hz_fb_create hz_fb_destroy
+// Entry: the null test (fn in the message), HandleLock, the handle's device current, the state back
+// from the per-sample engine.  The mutex is recursive: hz_fb_process_events* call hz_fb_process*.
+struct Entry {
+    std::optional<HandleLock> lk;
+    int status = HZ_OK;   // HZ_TRY it
+    Entry(hz_fb* h, const char* fn, bool state_back = true) {
+        if (!h) {
+            hz::set_error("%s: null hz_fb handle", fn);
+            status = HZ_E_INVALID;
+            return;
+        }
+        lk.emplace(h);
+        status = hz::hip_status(hipSetDevice(h->device), "hipSetDevice");
+        if (status == HZ_OK && state_back) status = fb_rt_stop(h);
+    }
+};
 
 }  // namespace hz_fbi

@@ -1498,10 +1498,8 @@ int fb_launch_lti(hz_fb* h, int gi, const double* d_in, double* d_out, long n) {
                                (const double*)part, a.n_pad, S, len, d_out + off);
             HZ_TRY_HIP(hipGetLastError());
             if (e) HZ_TRY_HIP(hipEventRecord(e[4], h->stream));
-            h->xcur ^= 1;
-            h->scur ^= 1;
             h->prof_launches += h->prof ? 1 : 0;
-            fb_mirror_advance(h, len);
+            fb_advance(h, len);
             continue;
         }
         // one chunk: the reduce stays on the caller's stream (no cross-stream round trip)
@@ -1522,10 +1520,8 @@ int fb_launch_lti(hz_fb* h, int gi, const double* d_in, double* d_out, long n) {
         HZ_TRY_HIP(hipGetLastError());
         if (e) HZ_TRY_HIP(hipEventRecord(e[4], rs));
         if (nchunks > 1) HZ_TRY_HIP(hipEventRecord(ev_red[k], rs));
-        h->xcur ^= 1;
-        h->scur ^= 1;
         h->prof_launches += h->prof ? 1 : 0;
-        fb_mirror_advance(h, len);
+        fb_advance(h, len);
     }
     // the caller's stream sees the whole output
     if (nchunks > 1 && !gemm) HZ_TRY_HIP(hipStreamWaitEvent(h->stream, ev_red[nchunks - 1], 0));

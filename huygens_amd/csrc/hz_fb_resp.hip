@@ -1179,11 +1179,9 @@ int fb_launch_resp(hz_fb* h, const double* d_in, double* d_out, long n) {
         if (e) HZ_TRY_HIP(hipEventRecord(e[4], h->stream));
         R.implicit = false;
     }
-    h->scur ^= 1;
-    h->xcur ^= 1;
     h->prof_launches += h->prof ? 1 : 0;
     ++R.calls;
-    fb_mirror_advance(h, n);
+    fb_advance(h, n);
     return HZ_OK;
 }
 
@@ -1263,7 +1261,8 @@ int hz_fb_set_response(hz_fb* h, int mode) {
         hz::set_error("hz_fb_set_response: mode must be HZ_FB_RESP_OFF, _EAGER or _LAZY");
         return HZ_E_INVALID;
     }
-    HZ_TRY_HIP(hipSetDevice(h->device));
+    hz_fbi::Entry entry(h, "hz_fb_set_response");
+    HZ_TRY(entry.status);
     HZ_TRY(hz_fbi::fb_resp_materialize(h));
     h->resp.mode = mode;
     h->resp.armed = false;   // a time-sharded handle re-arms (on every rank) for the new mode
@@ -1273,8 +1272,9 @@ int hz_fb_set_response(hz_fb* h, int mode) {
 
 int hz_fb_set_bank_response(hz_fb* h, const double* resp, long count) {
     if (!h || (count > 0 && !resp) || count < 0) return HZ_E_INVALID;
-    HZ_TRY_HIP(hipSetDevice(h->device));
-    HZ_TRY(hz_fbi::fb_upload_staged(h));
+    hz_fbi::Entry entry(h, "hz_fb_set_bank_response");
+    HZ_TRY(entry.status);
+    HZ_TRY(hz_fbi::fb_upload(h));
     if (count == 0) {
         h->resp.over_valid = false;
         h->resp.h_valid = false;
@@ -1303,6 +1303,7 @@ int hz_fb_set_bank_response(hz_fb* h, const double* resp, long count) {
 
 int hz_fb_set_time_shard(hz_fb* h, int rank, int world) {
     if (!h || world < 1 || rank < 0 || rank >= world) return HZ_E_INVALID;
+    hz_fbi::HandleLock lk(h);
     h->resp.shard_rank = rank;
     h->resp.shard_world = world;
     h->resp.armed = false;
@@ -1317,7 +1318,8 @@ int hz_fb_set_time_shard_fill(hz_fb* h, int zero_outside) {
 
 int hz_fb_stationary_ready(hz_fb* h, long n, int* ready) {
     if (!h || !ready || n < 0) return HZ_E_INVALID;
-    HZ_TRY_HIP(hipSetDevice(h->device));
+    hz_fbi::Entry entry(h, "hz_fb_stationary_ready", false);
+    HZ_TRY(entry.status);
     const bool conv = h->order > 0 && n >= 16 && hz_fbi::fb_converged(h);
     *ready = hz_fbi::fb_resp_eligible(h, n, conv) ? 1 : 0;
     return HZ_OK;
@@ -1325,6 +1327,7 @@ int hz_fb_stationary_ready(hz_fb* h, long n, int* ready) {
 
 int hz_fb_arm_time_shard(hz_fb* h, int armed) {
     if (!h) return HZ_E_INVALID;
+    hz_fbi::HandleLock lk(h);
     if (armed && !hz_fbi::fb_resp_time_sharded(h)) {
         hz::set_error("hz_fb_arm_time_shard: no time shard set (hz_fb_set_bank_response + hz_fb_set_time_shard)");
         return HZ_E_STATE;
@@ -1396,8 +1399,9 @@ int hz_fb_response_info(hz_fb* h, long* horizon, long* run, int* implicit_state,
 
 int hz_fb_get_response(hz_fb* h, double* out, long count) {
     if (!h || !out || count < 0) return HZ_E_INVALID;
-    HZ_TRY_HIP(hipSetDevice(h->device));
-    HZ_TRY(hz_fbi::fb_upload_staged(h));
+    hz_fbi::Entry entry(h, "hz_fb_get_response", false);
+    HZ_TRY(entry.status);
+    HZ_TRY(hz_fbi::fb_upload(h));
     if (h->order == 0) {
         hz::set_error("hz_fb_get_response: order 0 bank");
         return HZ_E_INVALID;

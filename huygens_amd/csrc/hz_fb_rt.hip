@@ -20,7 +20,7 @@
 // or tick-rotation converts back (the rows and the spare row into ystate / xhist).
 //
 // Setters while samples run (the reference's MIDI thread, tests/filterbank.cpp:217-252 against
-// the audio thread's 200-210): every entry point takes the handle's lock; a boost / mix / open or a
+// the audio thread's 200-210): they and the samples take the handle's lock; a boost / mix / open or a
 // coefficients() call reaches the next sample's request as a payload the server copies into the
 // device arrays (no conversion, no restart), so it applies from the next operator() on -- the
 // documented application point.
@@ -84,21 +84,51 @@ void fb_rt_target_setter(hz_fb* h, int l) {
     T.sp_gen = h->pg_gen;
 }
 
+// F, B -> dst [N][2O+1], the op's layout (forward, then back)
+static void rt_pack_coef(const hz_fb* h, double* dst) {
+    const int O = h->order;
+    for (int n = 0; n < h->N; ++n, dst += 2 * O + 1) {
+        for (int i = 0; i <= O; ++i) dst[i] = h->F[(size_t)n * (O + 1) + i];
+        for (int k = 0; k < O; ++k) dst[O + 1 + k] = h->B[(size_t)n * O + k];
+    }
+}
+
+// the input ring after `ticks` bare ticks (ring order; rotated right per tick)
+static void rt_rotate_ring(hz_fb::Rt& T, int O, long ticks) {
+    for (long q = 0; q < ticks; ++q) {
+        const double t0 = T.xr[O];
+        for (int k = O; k >= 1; --k) T.xr[k] = T.xr[k - 1];
+        T.xr[0] = t0;
+    }
+}
+
+// bare ticks whose ring row is not kept: the error of `who` (member >= 0: of a sample_many group);
+// -> ticks to apply, or a negative code
+static long rt_bare_ticks(const hz_fb* h, const char* who, int member) {
+    const hz_fb::Rt& T = h->rt;
+    const long ticks = h->order > 0 ? T.pending_ticks % (h->order + 1) : 0;
+    const bool spare_known = T.active ? T.spare_known : h->spare_ok;   // the ring row a bare tick exposes
+    if (T.computed || ticks == 0 || spare_known) return ticks;
+    if (member < 0)
+        hz::set_error("%s: tick() without operator() after a block call or set_state: the ring row "
+                      "it would reuse (O+1 samples back) is not kept", who);
+    else
+        hz::set_error("%s: tick() without operator() after a block call or set_state (member %d)", who, member);
+    return HZ_E_STATE;
+}
+
 // the state into ring rows, the coefficients into the op's layout, the input ring to the host
 static int rt_enter(hz_fb* h) {
     hz_fb::Rt& T = h->rt;
     const int O = h->order, N = h->N;
-    HZ_TRY(fb_upload_staged(h));
+    HZ_TRY(fb_upload(h));
     HZ_TRY(fb_resp_materialize(h));
     const size_t nc = (size_t)N * (2 * O + 1), nr = (size_t)N * (O + 1);
     if (nc + nr > T.d_coef.cap()) HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     HZ_TRY(T.d_coef.reserve(nc + nr));
     HZ_TRY(T.pin1.reserve(16));
     T.h_coef.resize(nc);
-    for (int n = 0; n < N; ++n) {
-        for (int i = 0; i <= O; ++i) T.h_coef[(size_t)n * (2 * O + 1) + i] = h->F[(size_t)n * (O + 1) + i];
-        for (int k = 0; k < O; ++k) T.h_coef[(size_t)n * (2 * O + 1) + O + 1 + k] = h->B[(size_t)n * O + k];
-    }
+    rt_pack_coef(h, T.h_coef.data());
     HZ_TRY_HIP(hipMemcpyAsync(T.d_coef, T.h_coef.data(), sizeof(double) * nc, hipMemcpyHostToDevice, h->stream));
     const int spare = h->spare_ok ? 1 : 0;
     hipLaunchKernelGGL(fb_rt_enter_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream,
@@ -157,6 +187,18 @@ int fb_rt_stop(hz_fb* h) {
     return HZ_OK;
 }
 
+// into the per-sample layout; out of it first after a coefficient-stream call (the pending ticks stay)
+static int rt_reenter(hz_fb* h) {
+    hz_fb::Rt& T = h->rt;
+    if (T.active) {
+        const long keep = T.pending_ticks;
+        T.pending_ticks = 0;
+        HZ_TRY(fb_rt_stop(h));
+        T.pending_ticks = keep;
+    }
+    return rt_enter(h);
+}
+
 static int sample_locked(hz_fb* h, double x, int dist_id, double param, double* y);
 static void tick_locked(hz_fb* h);
 
@@ -175,13 +217,8 @@ static int sample_locked(hz_fb* h, double x, int dist_id, double param, double* 
     HZ_TRY_HIP(hipSetDevice(h->device));
     hz_fb::Rt& T = h->rt;
     const int O = h->order, N = h->N;
-    const long ticks = O > 0 ? T.pending_ticks % (O + 1) : 0;
-    const bool spare_known = T.active ? T.spare_known : h->spare_ok;   // the ring row a bare tick exposes
-    if (!T.computed && ticks > 0 && !spare_known) {
-        hz::set_error("hz_fb_sample: tick() without operator() after a block call or set_state: the ring row "
-                      "it would reuse (O+1 samples back) is not kept");
-        return HZ_E_STATE;
-    }
+    const long ticks = rt_bare_ticks(h, "hz_fb_sample", -1);
+    if (ticks < 0) return (int)ticks;
     hz_rt::Server* srv = hz_rt::server(h->device);
     if (!srv) {
         hz::set_error("hz_fb_sample: no per-sample server on device %d", h->device);
@@ -191,15 +228,7 @@ static int sample_locked(hz_fb* h, double x, int dist_id, double param, double* 
         hz_rt::quiesce(srv);
         T.many = false;
     }
-    if (!T.active || h->tv_pending) {
-        if (T.active) {   // a coefficient stream call left a row staged: convert back and in again
-            const long keep = T.pending_ticks;
-            T.pending_ticks = 0;
-            HZ_TRY(hz_fbi::fb_rt_stop(h));
-            T.pending_ticks = keep;
-        }
-        HZ_TRY(hz_fbi::rt_enter(h));
-    }
+    if (!T.active || h->tv_pending) HZ_TRY(rt_reenter(h));
     hz_rt::FbArgs a{};
     const size_t nc = (size_t)N * (2 * O + 1);
     a.R = T.d_coef + nc;
@@ -239,22 +268,13 @@ static int sample_locked(hz_fb* h, double x, int dist_id, double param, double* 
         if (tg) hz_fbi::sparse_clear(h);
         if (cf) {
             HZ_TRY(hz_fbi::fb_tv_materialize(h));
-            for (int n = 0; n < N; ++n) {
-                double* r = p + at + (size_t)n * (2 * O + 1);
-                for (int i = 0; i <= O; ++i) r[i] = h->F[(size_t)n * (O + 1) + i];
-                for (int k = 0; k < O; ++k) r[O + 1 + k] = h->B[(size_t)n * O + k];
-            }
+            rt_pack_coef(h, p + at);
             a.reload_coef = (const double*)hz_rt::dev(srv, p + at);
         }
         T.pg_gen = h->pg_gen;
         T.coef_gen = h->coef_gen;
     }
-    // the input ring after the bare ticks (ring order; rotated right per tick)
-    for (long q = 0; q < ticks; ++q) {
-        const double t0 = T.xr[O];
-        for (int k = O; k >= 1; --k) T.xr[k] = T.xr[k - 1];
-        T.xr[0] = t0;
-    }
+    rt_rotate_ring(T, O, ticks);
     const bool compute = !T.computed;
     a.x = x;
     a.param = param;
@@ -357,10 +377,7 @@ static int many_apply_setters(hz_fb* h) {
         HZ_TRY(fb_tv_materialize(h));
         const size_t nc = (size_t)N * (2 * O + 1);
         T.h_coef.resize(nc);
-        for (int n = 0; n < N; ++n) {
-            for (int i = 0; i <= O; ++i) T.h_coef[(size_t)n * (2 * O + 1) + i] = h->F[(size_t)n * (O + 1) + i];
-            for (int k = 0; k < O; ++k) T.h_coef[(size_t)n * (2 * O + 1) + O + 1 + k] = h->B[(size_t)n * O + k];
-        }
+        rt_pack_coef(h, T.h_coef.data());
         HZ_TRY_HIP(hipMemcpy(T.d_coef, T.h_coef.data(), sizeof(double) * nc, hipMemcpyHostToDevice));
     }
     T.pg_gen = h->pg_gen;
@@ -382,12 +399,7 @@ static int sample_many_locked(hz_fb* const* hs, int H, const double* x, int dist
     bool fresh = false;
     for (int m = 0; m < H; ++m) {
         hz_fb::Rt& T = hs[m]->rt;
-        const long ticks = O > 0 ? T.pending_ticks % (O + 1) : 0;
-        const bool spare_known = T.active ? T.spare_known : hs[m]->spare_ok;
-        if (!T.computed && ticks > 0 && !spare_known) {
-            hz::set_error("hz_fb_sample_many: tick() without operator() after a block call or set_state (member %d)", m);
-            return HZ_E_STATE;
-        }
+        if (rt_bare_ticks(hs[m], "hz_fb_sample_many", m) < 0) return HZ_E_STATE;
         if (!T.active || hs[m]->tv_pending || !T.many || T.pg_gen != hs[m]->pg_gen || T.coef_gen != hs[m]->coef_gen)
             fresh = true;
     }
@@ -396,15 +408,7 @@ static int sample_many_locked(hz_fb* const* hs, int H, const double* x, int dist
         for (int m = 0; m < H; ++m) {
             hz_fb* h = hs[m];
             hz_fb::Rt& T = h->rt;
-            if (!T.active || h->tv_pending) {
-                if (T.active) {
-                    const long keep = T.pending_ticks;
-                    T.pending_ticks = 0;
-                    HZ_TRY(fb_rt_stop(h));
-                    T.pending_ticks = keep;
-                }
-                HZ_TRY(rt_enter(h));
-            }
+            if (!T.active || h->tv_pending) HZ_TRY(rt_reenter(h));
             HZ_TRY(many_apply_setters(h));
             T.many = true;
         }
@@ -436,11 +440,7 @@ static int sample_many_locked(hz_fb* const* hs, int H, const double* x, int dist
     for (int m = 0; m < H; ++m) {
         hz_fb::Rt& T = hs[m]->rt;
         const long ticks = O > 0 ? T.pending_ticks % (O + 1) : 0;
-        for (long q = 0; q < ticks; ++q) {   // the input ring after the bare ticks
-            const double t0 = T.xr[O];
-            for (int k = O; k >= 1; --k) T.xr[k] = T.xr[k - 1];
-            T.xr[0] = t0;
-        }
+        rt_rotate_ring(T, O, ticks);
         const bool compute = !T.computed;
         a->meta |= (unsigned long long)(ticks | (compute ? 8 : 0)) << (4 * m);
         xv[m * (O + 2)] = x[m];

@@ -385,11 +385,8 @@ extern "C" {
 
 int hz_fb_process_tv_device(hz_fb* h, const double* d_in, double* d_out, size_t n, int kind,
                             const double* d_stream, double param) {
-    if (!h) {
-        hz::set_error("null hz_fb handle");
-        return HZ_E_INVALID;
-    }
-    HZ_TRY_HIP(hipSetDevice(h->device));
+    hz_fbi::Entry entry(h, "hz_fb_process_tv_device", false);
+    HZ_TRY(entry.status);
     const int O = h->order;
     if ((kind != HZ_FB_TV_COEFFS && kind != HZ_FB_TV_RESONANT) || (kind == HZ_FB_TV_RESONANT && O != 2)) {
         hz::set_error("hz_fb_process_tv: kind %d needs %s", kind,
@@ -401,33 +398,21 @@ int hz_fb_process_tv_device(hz_fb* h, const double* d_in, double* d_out, size_t 
         hz::set_error("hz_fb_process_tv: null buffer");
         return HZ_E_INVALID;
     }
-    if (h->rt.computed) {   // after operator() without tick(): the cached sample first (fb_rt_resolve)
-        double y0 = 0;
-        const int k = hz_fbi::fb_rt_resolve(h, &y0);
-        if (k < 0) return k;
-        double* pin0 = hz_fbi::fb_rt_cached_slot(h);
-        *pin0 = y0;
-        HZ_TRY_HIP(hipMemcpyAsync(d_out, pin0, sizeof(double), hipMemcpyHostToDevice, h->stream));
-        const long row0 = kind == HZ_FB_TV_COEFFS ? (2 * O + 1) * (long)h->N : (long)h->N;
-        ++d_in;
-        ++d_out;
-        d_stream += row0;
-        if (--n == 0) return HZ_OK;
-    }
-    HZ_TRY(hz_fbi::fb_rt_stop(h));   // the state back from the per-sample engine
+    const long N = h->N, G = (N + kThreads - 1) / kThreads;
+    const long row = kind == HZ_FB_TV_COEFFS ? (2 * O + 1) * N : N;
+    const int k0 = hz_fbi::fb_block_begin(h, d_out, true);   // the cached sample takes the stream's first row
+    if (k0 < 0) return k0;
+    if ((n -= k0) == 0) return HZ_OK;
+    d_in += k0;
+    d_out += k0;
+    d_stream += k0 * row;
     // pin / gin.  This call's last row supersedes a pending one, and the stream kernel does not
     // read the staged coefficients, so their rebuild waits for the next plain call.
     h->tv_pending = false;
-    const bool dirty_coef = h->dirty_coef;
-    h->dirty_coef = false;
-    const int up = hz_fbi::fb_upload_staged(h);
-    h->dirty_coef = dirty_coef;
-    HZ_TRY(up);
+    HZ_TRY(hz_fbi::fb_upload(h, false));
     HZ_TRY(hz_fbi::fb_resp_materialize(h));   // the stream kernel reads the band states
     hz_fbi::fb_resp_invalidate(h, true);      // and leaves other coefficients behind
-    const long N = h->N, G = (N + kThreads - 1) / kThreads;
     const long chunk = std::max(1L, std::min(1L << 20, kPartBytes / (long)sizeof(double) / G));
-    const long row = kind == HZ_FB_TV_COEFFS ? (2 * O + 1) * N : N;
     const long need = G * std::min((long)n, chunk);
     HZ_TRY(h->d_partial.reserve((size_t)need));
     const tv_fn k = tv_pick(O, kind, h->dist_id);
@@ -475,9 +460,7 @@ int hz_fb_process_tv_device(hz_fb* h, const double* d_in, double* d_out, size_t 
             HZ_TRY_HIP(hipEventRecord(e[4], h->stream));
             ++h->prof_launches;
         }
-        h->scur ^= 1;
-        h->xcur ^= 1;
-        hz_fbi::fb_mirror_advance(h, len);
+        hz_fbi::fb_advance(h, len);
     }
     h->last_path = HZ_FB_PATH_GENERAL;
     h->spare_ok = n == 1;   // see hz_fb_tick
@@ -498,11 +481,8 @@ int hz_fb_process_tv_device(hz_fb* h, const double* d_in, double* d_out, size_t 
 
 int hz_fb_process_tv(hz_fb* h, const double* in, double* out, size_t n, int kind, const double* stream,
                      double param) {
-    if (!h) {
-        hz::set_error("null hz_fb handle");
-        return HZ_E_INVALID;
-    }
-    HZ_TRY_HIP(hipSetDevice(h->device));
+    hz_fbi::Entry entry(h, "hz_fb_process_tv", false);
+    HZ_TRY(entry.status);
     if (n == 0) return hz_fb_process_tv_device(h, nullptr, nullptr, 0, kind, nullptr, param);
     if (!in || !out || !stream) {
         hz::set_error("hz_fb_process_tv: null buffer");

@@ -781,22 +781,33 @@ int fb_groups(const hz_fb* h, bool ev = false) {
     return (h->N + per - 1) / per;
 }
 
-int fb_upload(hz_fb* h) {
+// chunk bound so the partial slab stays <= ~1 GiB
+long fb_max_chunk(const hz_fb* h, bool ev = false) {
+    const long G = fb_groups(h, ev);
+    long c = (1L << 27) / std::max(1L, G);  // doubles per row
+    c = std::max<long>(kTile, (c / kTile) * kTile);
+    return c;
+}
+
+}  // namespace
+
+int hz_fbi::fb_upload(hz_fb* h, bool coefficients) {
     bool uploaded = false;
+    const bool dirty_coef = coefficients && h->dirty_coef;   // (targets only: as if they were clean)
     // LAZY band states of a stationary call follow from the coefficients and pre-amps it ran
     // with: materialise them before new ones reach the device
-    if (h->resp.implicit && (h->dirty_coef || h->dirty_pin || h->tv_pending)) HZ_TRY(hz_fbi::fb_resp_materialize(h));
+    if (h->resp.implicit && (dirty_coef || h->dirty_pin || h->tv_pending)) HZ_TRY(hz_fbi::fb_resp_materialize(h));
     // gains only, while the bank streams stationary: a transient of the streaming engine instead of
     // a new response and K samples of history (hz_fb_stream.hip fb_stream_gain_setter; its launch
     // also brings the smoothers up to date and writes d_gin)
-    const int transient = (h->dirty_gin && !h->dirty_pin && !h->dirty_coef && !h->tv_pending)
+    const int transient = (h->dirty_gin && !h->dirty_pin && !dirty_coef && !h->tv_pending)
                               ? hz_fbi::fb_stream_gain_setter(h) : 0;
     if (transient < 0) HZ_TRY(transient);   // a launch failed: nothing below runs on the half-applied update
     // streamed samples bring the smoothers up to date lazily, toward the targets they ran with:
     // apply them before new targets (mix / boost) reach the device
     if (!transient && (h->dirty_pin || h->dirty_gin)) HZ_TRY(hz_fbi::fb_stream_upkeep(h));
     HZ_TRY(hz_fbi::fb_tv_materialize(h));
-    if (h->dirty_coef) {
+    if (coefficients && h->dirty_coef) {
         const int O = h->order;
         h->h_rec.assign((size_t)h->N * h->rec, 0.0);
         for (int n = 0; n < h->N; ++n)
@@ -836,16 +847,6 @@ int fb_upload(hz_fb* h) {
     return HZ_OK;
 }
 
-// chunk bound so the partial slab stays <= ~1 GiB
-long fb_max_chunk(const hz_fb* h, bool ev = false) {
-    const long G = fb_groups(h, ev);
-    long c = (1L << 27) / std::max(1L, G);  // doubles per row
-    c = std::max<long>(kTile, (c / kTile) * kTile);
-    return c;
-}
-
-}  // namespace
-
 namespace hz_fbi {
 
 // five timing events per launch (start, mix start, mix end, reduce start, reduce end)
@@ -857,9 +858,6 @@ int fb_prof_events(hz_fb* h, hipEvent_t** e) {
     h->ev_rep[g - 1] = 1;
     return HZ_OK;
 }
-
-// staged setters -> device (the per-sample coefficient path, hz_fb_tv.hip, reads pin / gin)
-int fb_upload_staged(hz_fb* h) { return fb_upload(h); }
 
 // host mirror of the closed-form smoother end state written by every launch
 // (pgstate_next = pin + sp^n (pre - pin), likewise for the gains)
@@ -985,10 +983,8 @@ int fb_launch_general(hz_fb* h, const double* d_in, double* d_out, long n, const
                              hz::mix::SlabStore<double>{d_out + off});
         HZ_TRY_HIP(hipGetLastError());
         if (e) HZ_TRY_HIP(hipEventRecord(e[4], h->stream));
-        h->xcur ^= 1;
-        h->scur ^= 1;
         h->prof_launches += h->prof ? 1 : 0;
-        fb_mirror_advance(h, len);
+        fb_advance(h, len);
     }
     return HZ_OK;
 }
@@ -1063,13 +1059,6 @@ int fb_launch(hz_fb* h, const double* d_in, double* d_out, long n) {
     return fb_resp_track(h, d_in, n, conv);
 }
 
-int fb_check(hz_fb* h) {
-    HZ_TRY(hz::check_handle(h, "hz_fb"));
-    // every device-side use of the state needs it back from the per-sample engine
-    return hz_fbi::fb_rt_stop(h);
-}
-
-
 // global band index -> local, or -1 when outside this shard
 int fb_local(const hz_fb* h, int n) {
     if (n < h->band_begin || n >= h->band_begin + h->N) return -1;
@@ -1095,9 +1084,18 @@ int fb_tick_rotate(hz_fb* h) {
                        (const double*)h->d_ystate[h->scur], h->d_ystate[h->scur ^ 1], (const double*)h->d_pg[h->scur],
                        h->d_pg[h->scur ^ 1], (const double*)h->d_xhist[h->xcur], h->d_xhist[h->xcur ^ 1], N, O);
     HZ_TRY_HIP(hipGetLastError());
-    h->scur ^= 1;
-    h->xcur ^= 1;
+    fb_advance(h, 0);
     return HZ_OK;
+}
+
+int fb_block_begin(hz_fb* h, double* out0, bool out_is_device) {
+    if (!out0 || !h->rt.computed) return fb_rt_stop(h);   // (HZ_OK is 0)
+    // (the pinned slot is pin1[15]: rt_enter / fb_rt_stop inside the resolve use pin1[0..O-1] and [8..8+O-1] only)
+    double* y0 = out_is_device ? fb_rt_cached_slot(h) : out0;
+    const int k = fb_rt_resolve(h, y0);   // (the state comes back in it)
+    if (k > 0 && out_is_device)
+        HZ_TRY_HIP(hipMemcpyAsync(out0, y0, sizeof(double), hipMemcpyHostToDevice, h->stream));
+    return k;
 }
 }  // namespace hz_fbi
 
@@ -1308,22 +1306,13 @@ int hz_fb_process_device(hz_fb* h, const double* d_in, double* d_out, size_t n) 
         hz::set_error("hz_fb_process_device: null handle or buffer");
         return HZ_E_INVALID;
     }
-    hz_fbi::HandleLock lk(h);
-    if (h->rt.computed) {   // the cached sample first (fb_rt_resolve), copied from pinned memory
-        HZ_TRY_HIP(hipSetDevice(h->device));
-        double y0 = 0;
-        const int k = hz_fbi::fb_rt_resolve(h, &y0);
-        if (k < 0) return k;
-        double* pin0 = hz_fbi::fb_rt_cached_slot(h);
-        *pin0 = y0;
-        HZ_TRY_HIP(hipMemcpyAsync(d_out, pin0, sizeof(double), hipMemcpyHostToDevice, h->stream));
-        ++d_in;
-        ++d_out;
-        if (--n == 0) return HZ_OK;
-    }
-    HZ_TRY(fb_check(h));
+    hz_fbi::Entry entry(h, "hz_fb_process_device", false);
+    HZ_TRY(entry.status);
+    const int k = fb_block_begin(h, d_out, true);
+    if (k < 0) return k;
+    if ((n -= k) == 0) return HZ_OK;
     HZ_TRY(fb_upload(h));
-    return fb_launch(h, d_in, d_out, (long)n);
+    return fb_launch(h, d_in + k, d_out + k, (long)n);
 }
 
 int hz_fb_process(hz_fb* h, const double* in, double* out, size_t n) {
@@ -1332,16 +1321,13 @@ int hz_fb_process(hz_fb* h, const double* in, double* out, size_t n) {
         hz::set_error("hz_fb_process: null handle or buffer");
         return HZ_E_INVALID;
     }
-    hz_fbi::HandleLock lk(h);
-    if (h->rt.computed) {   // the cached sample first (fb_rt_resolve)
-        HZ_TRY_HIP(hipSetDevice(h->device));
-        const int k = hz_fbi::fb_rt_resolve(h, out);
-        if (k < 0) return k;
-        ++in;
-        ++out;
-        if (--n == 0) return HZ_OK;
-    }
-    HZ_TRY(fb_check(h));
+    hz_fbi::Entry entry(h, "hz_fb_process", false);
+    HZ_TRY(entry.status);
+    const int k = fb_block_begin(h, out, false);
+    if (k < 0) return k;
+    if ((n -= k) == 0) return HZ_OK;
+    in += k;
+    out += k;
     HZ_TRY(h->d_in.reserve(n));
     HZ_TRY(h->d_out.reserve(n));
     HZ_TRY(fb_upload(h));
@@ -1486,21 +1472,13 @@ int hz_fb_process_events_device(hz_fb* h, const double* d_in, double* d_out, siz
         hz::set_error("hz_fb_process_events_device: null handle or buffer");
         return HZ_E_INVALID;
     }
-    hz_fbi::HandleLock lk(h);
+    hz_fbi::Entry entry(h, "hz_fb_process_events_device", false);
+    HZ_TRY(entry.status);
     HZ_TRY(fb_events_check(h, n, ev, nev, "hz_fb_process_events_device"));
     if (nev == 0) return hz_fb_process_device(h, d_in, d_out, n);
-    long pos = 0;
-    if (n > 0 && h->rt.computed) {   // the cached sample first, as hz_fb_process_device: setters before
-        HZ_TRY_HIP(hipSetDevice(h->device));   // it change no sample already computed
-        double y0 = 0;
-        const int k = hz_fbi::fb_rt_resolve(h, &y0);
-        if (k < 0) return k;
-        double* pin0 = hz_fbi::fb_rt_cached_slot(h);
-        *pin0 = y0;
-        HZ_TRY_HIP(hipMemcpyAsync(d_out, pin0, sizeof(double), hipMemcpyHostToDevice, h->stream));
-        pos = 1;
-    }
-    HZ_TRY(fb_check(h));
+    // (the cached sample first: setters before it change no sample already computed)
+    long pos = fb_block_begin(h, n > 0 ? d_out : nullptr, true);
+    if (pos < 0) return (int)pos;
     const long N = (long)n, chunk = fb_max_chunk(h, true);
     bool ran = false;
     int i = 0;
@@ -1532,7 +1510,8 @@ int hz_fb_process_events(hz_fb* h, const double* in, double* out, size_t n, cons
         hz::set_error("hz_fb_process_events: null handle or buffer");
         return HZ_E_INVALID;
     }
-    hz_fbi::HandleLock lk(h);
+    hz_fbi::Entry entry(h, "hz_fb_process_events", false);
+    HZ_TRY(entry.status);
     HZ_TRY(fb_events_check(h, n, ev, nev, "hz_fb_process_events"));
     if (nev == 0) return hz_fb_process(h, in, out, n);
     if (n > 0) {
@@ -1549,7 +1528,8 @@ int hz_fb_process_events(hz_fb* h, const double* in, double* out, size_t n, cons
 }
 
 int hz_fb_set_stream(hz_fb* h, void* s) {
-    HZ_TRY(fb_check(h));
+    hz_fbi::Entry entry(h, "hz_fb_set_stream");
+    HZ_TRY(entry.status);
     return h->stream.rebind(s, hz::NullMeans::Private);
 }
 
@@ -1560,7 +1540,8 @@ int hz_fb_get_stream(hz_fb* h, void** s) {
 }
 
 int hz_fb_synchronize(hz_fb* h) {
-    HZ_TRY(fb_check(h));
+    hz_fbi::Entry entry(h, "hz_fb_synchronize");
+    HZ_TRY(entry.status);
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     return HZ_OK;
 }
@@ -1572,9 +1553,8 @@ int hz_fb_state_size(hz_fb* h, size_t* count) {
 }
 
 int hz_fb_get_state(hz_fb* h, double* buf, size_t count) {
-    if (!h) return HZ_E_INVALID;
-    hz_fbi::HandleLock lk(h);
-    HZ_TRY(fb_check(h));
+    hz_fbi::Entry entry(h, "hz_fb_get_state");
+    HZ_TRY(entry.status);
     size_t need;
     hz_fb_state_size(h, &need);
     if (!buf || count < need) return HZ_E_INVALID;
@@ -1590,9 +1570,8 @@ int hz_fb_get_state(hz_fb* h, double* buf, size_t count) {
 }
 
 int hz_fb_set_state(hz_fb* h, const double* buf, size_t count) {
-    if (!h) return HZ_E_INVALID;
-    hz_fbi::HandleLock lk(h);
-    HZ_TRY(fb_check(h));
+    hz_fbi::Entry entry(h, "hz_fb_set_state");
+    HZ_TRY(entry.status);
     size_t need;
     hz_fb_state_size(h, &need);
     if (!buf || count < need) return HZ_E_INVALID;
@@ -1614,12 +1593,10 @@ int hz_fb_set_state(hz_fb* h, const double* buf, size_t count) {
 }
 
 int hz_fb_tick(hz_fb* h) {
-    if (!h) return HZ_E_INVALID;
-    hz_fbi::HandleLock lk(h);
-    HZ_TRY(fb_check(h));
+    hz_fbi::Entry entry(h, "hz_fb_tick");
+    HZ_TRY(entry.status);
     return hz_fbi::fb_tick_rotate(h);
 }
-
 
 int hz_fb_setter_seq(hz_fb* h, long long* seq) {
     if (!h || !seq) return HZ_E_INVALID;
@@ -1672,7 +1649,8 @@ int hz_fb_last_path(hz_fb* h, int* path) {
 }
 
 int hz_fb_profile(hz_fb* h, int enable) {
-    HZ_TRY(fb_check(h));
+    hz_fbi::Entry entry(h, "hz_fb_profile");
+    HZ_TRY(entry.status);
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     h->prof = enable != 0;
     h->prof_rep = enable > 1 ? std::min(enable, 64) : 1;
@@ -1682,7 +1660,8 @@ int hz_fb_profile(hz_fb* h, int enable) {
 }
 
 int hz_fb_profile_read(hz_fb* h, double* segment_ms, double* mix_ms, double* reduce_ms, long* launches) {
-    HZ_TRY(fb_check(h));
+    hz_fbi::Entry entry(h, "hz_fb_profile_read");
+    HZ_TRY(entry.status);
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
     if (h->stream_red) HZ_TRY_HIP(hipStreamSynchronize(h->stream_red));
     double sg = 0, m = 0, r = 0;

@@ -113,8 +113,9 @@ int hz_fb_sample_tick(hz_fb* h);
 int hz_fb_sample_many(hz_fb* const* handles, int count, const double* x, int dist_id, double param, double* y);
 /* the number of per-sample calls served when the last setter (coefficients / boost / mix / open)
  * ran: the setter applies from that call on (setters may come from another thread while samples
- * run -- every entry point holds the handle's lock; the reference's MIDI thread,
- * tests/filterbank.cpp:217-252) */
+ * run -- the per-sample calls and every call that touches the staged parameters, the state or
+ * the stream hold the handle's lock; scalar tuning and *_info calls take none; the reference's
+ * MIDI thread, tests/filterbank.cpp:217-252) */
 int hz_fb_setter_seq(hz_fb* h, long long* seq);
 /* whether the handle is in per-sample mode, samples served, server workgroups taking part */
 int hz_fb_sample_info(hz_fb* h, int* active, long long* served, int* groups);

@@ -108,6 +108,9 @@ _SIGS = {
     "hz_fb_tune_response": (I, [VP, L, L]),
     "hz_fb_tune_response_engine": (I, [VP, I]),
     "hz_fb_sample_many": (I, [C.POINTER(VP), I, PD, I, D, PD]),
+    "hz_fb_process_many_device": (I, [C.POINTER(VP), I, VP, L, VP, L, SZ]),
+    "hz_fb_process_many": (I, [C.POINTER(VP), I, PD, L, PD, L, SZ]),
+    "hz_fb_many_info": (I, [VP, C.POINTER(L), C.POINTER(L)]),
     "hz_fb_response_engine": (I, [VP, C.POINTER(I), C.POINTER(I)]),
     "hz_fb_tune_modal": (I, [VP, I]),
     "hz_fb_modal_info": (I, [VP, C.POINTER(I), C.POINTER(I), C.POINTER(I), C.POINTER(I)]),

@@ -115,6 +115,19 @@ struct hz_fb {
     hz::PinBuf<char> h_ev;
     hz::Event ev_up;
     bool ev_up_pending = false;
+    // hz_fb_process_many.  As handles[0]: the batch's argument table, staged in pinned memory like
+    // the event rows above -- a ring of kManySlots tables, so the host runs that many calls ahead of
+    // the device before it waits for a slot's copy (many_up[slot]) -- and many_done, recorded after
+    // the batch's launch sequence for the members' streams to wait on.  As a member: many_ready,
+    // recorded on the member's stream before the sequence; how often such a call batched this handle
+    // or ran it alone.
+    static constexpr int kManySlots = 8;
+    hz::DevBuf<char> d_many;
+    hz::PinBuf<char> h_many;
+    hz::Event many_up[kManySlots], many_done, many_ready;
+    bool many_up_pending[kManySlots] = {};
+    unsigned many_slot = 0;
+    long many_batched = 0, many_sequential = 0;
     // host-buffer calls that take the streaming engine: pinned, device-mapped staging the kernel
     // reads and writes directly ([kStreamBlock] in, then [kStreamBlock] out, then 128 completion
     // flags (long long))
@@ -448,10 +461,11 @@ double* fb_rt_cached_slot(hz_fb* h);   // pinned host double for an async copy o
 //   sample path (SampleLock): hz_fb_sample hz_fb_sample_many hz_fb_sample_tick
 //   guarded, host staging only (HandleLock): hz_fb_coefficients hz_fb_boost hz_fb_boost_all hz_fb_mix
 //     hz_fb_mix_all hz_fb_open hz_fb_set_distortion hz_fb_setter_seq hz_fb_sample_info
-//     hz_fb_set_time_shard hz_fb_arm_time_shard
+//     hz_fb_set_time_shard hz_fb_arm_time_shard hz_fb_many_info
 //   guarded, device work (Entry; * = state_back false: fb_block_begin brings the state back, or
 //     the call leaves it with the per-sample engine): hz_fb_process* hz_fb_process_device*
 //     hz_fb_process_events* hz_fb_process_events_device* hz_fb_process_tv* hz_fb_process_tv_device*
+//     hz_fb_process_many* hz_fb_process_many_device* (every member's Entry, in address order)
 //     hz_fb_stationary_ready* hz_fb_get_response* hz_fb_set_response hz_fb_set_bank_response
 //     hz_fb_set_stream hz_fb_synchronize hz_fb_get_state hz_fb_set_state hz_fb_tick hz_fb_profile
 //     hz_fb_profile_read

@@ -26,6 +26,7 @@
 #include <cmath>
 #include <chrono>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -95,6 +96,36 @@ struct MixArgsEv : MixArgs {
     const double* ev_rows;
 };
 
+// hz_fb_process_many (fb_mix_kernel<.., MANY = true>): one table row per member of a batch.  The
+// members share the order, the functor, the workgroup size, n and with it the segment plan
+// (seg_len, nseg); everything else is the member's own, its partial slab and output row included.
+struct MixArgsMany : MixArgs {
+    double* out;   // the member's output row [n]
+    int groups;    // its band groups (<= the launch's grid.x)
+};
+struct MixArgsNone {};   // the batched form's second kernel argument
+
+// a generic pointer that is known to point to device memory, named global again (through an
+// integer: a direct cast pair is folded away and the accesses stay flat); as_constant: to memory
+// no kernel of the launch writes, wave-uniform (uniform reads through it are scalar loads)
+template <class T>
+__device__ __forceinline__ T* as_global(T* p) {
+    return (T*)(__attribute__((address_space(1))) T*)(unsigned long long)p;
+}
+__device__ __forceinline__ const double* as_constant(const double* p) {
+    const unsigned long long b = (unsigned long long)p;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((int)(b & 0xffffffffu));
+    const unsigned hi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
+    return (const double*)(const __attribute__((address_space(4))) double*)(((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ void global_pointers(MixArgs& a) {
+    a.pin = as_global(a.pin), a.gin = as_global(a.gin);
+    a.ystate = as_global(a.ystate), a.pgstate = as_global(a.pgstate);
+    a.ystate_next = as_global(a.ystate_next), a.pgstate_next = as_global(a.pgstate_next);
+    a.x = as_global(a.x), a.xhist = as_global(a.xhist), a.xhist_next = as_global(a.xhist_next);
+    a.partial = as_global(a.partial), a.segstate = as_global(a.segstate);
+}
+
 // LDS layout of one workgroup:
 //   xs   : the tile's input x[t0-16 .. t0+1023], padded one slot per 16 samples so
 //          lane c's reads (17c + k) hit 64 distinct banks (ds_read_b64)
@@ -145,10 +176,36 @@ using tag_walk = std::integral_constant<int, 2>;
 // included), and a tile with a row inside steps both smoothers per lane through the rows first
 // (ev_walk, values through the wave's own LDS rows) and reads them back sample by sample.  A band
 // without rows, and every EV = false instantiation, runs the code as it was.
-template <int O, int DIST, int NB, int MODE, int PF, bool EV = false>
-__global__ __launch_bounds__(wg_threads(PF)) void fb_mix_kernel(const double* __restrict__ rec,
-                                                                std::conditional_t<EV, MixArgsEv, MixArgs> a) {
+//
+// MANY (one band per wave): the batched form of hz_fb_process_many.  The first argument is a
+// device table with one MixArgsMany row per member and the second is empty: the workgroup's
+// member is blockIdx.z, its band group blockIdx.x and its time segment blockIdx.y; grid.x is the
+// largest member's group count, and a workgroup past its member's groups leaves at once.  The
+// row's pointers come out of memory as generic ones: they are named global again (global_pointers),
+// and the records constant (as_constant: nothing in the kernel writes them), so the wave-uniform
+// record reads stay scalar loads as in the other forms.
+template <int O, int DIST, int NB, int MODE, int PF, bool EV = false, bool MANY = false>
+__global__ __launch_bounds__(wg_threads(PF)) void fb_mix_kernel(
+    std::conditional_t<MANY, const MixArgsMany*, const double*> __restrict__ rec0,
+    std::conditional_t<MANY, MixArgsNone, std::conditional_t<EV, MixArgsEv, MixArgs>> a0) {
     static_assert(!EV || NB == 1, "the event form is built for one band per wave");
+    static_assert(!MANY || (NB == 1 && !EV), "the batched form is built for one band per wave, without events");
+    using Args = std::conditional_t<EV, MixArgsEv, MixArgs>;
+    [[maybe_unused]] MixArgs am;   // MANY: the member's row
+    const double* rec;
+    const Args* ap;
+    if constexpr (MANY) {
+        const MixArgsMany* t = rec0 + blockIdx.z;
+        if ((int)blockIdx.x >= t->groups) return;
+        am = *t;
+        global_pointers(am);
+        rec = as_constant(am.rec);
+        ap = &am;
+    } else {
+        rec = rec0;
+        ap = &a0;
+    }
+    const Args& a = *ap;
     constexpr int kRow = hz_fbev::kRow;
     const int* ev_off = nullptr;
     const double* ev_rows = nullptr;
@@ -589,10 +646,9 @@ __global__ __launch_bounds__(wg_threads(PF)) void fb_mix_kernel(const double* __
 // C^seg_len = (M16^64)^(seg_len/1024) by binary powering of the record's P[5]^2, in double-double
 // and applied as hi S + lo S (hz_dd.h: the same rounded power is applied nseg - 1 times).
 template <int O>
-__global__ __launch_bounds__(256) void fb_seg_carry_kernel(const double* __restrict__ rec,
-                                                           const double* __restrict__ ystate,
-                                                           double* __restrict__ segstate, int nbands,
-                                                           int nseg, long seg_tiles) {
+__device__ __forceinline__ void fb_seg_carry_body(const double* __restrict__ rec, const double* __restrict__ ystate,
+                                                  double* __restrict__ segstate, int nbands, int nseg,
+                                                  long seg_tiles) {
     using R = Rec<O>;
     using hz_dd::dd;
     const int band = blockIdx.x * blockDim.x + threadIdx.x;
@@ -631,6 +687,41 @@ __global__ __launch_bounds__(256) void fb_seg_carry_kernel(const double* __restr
             slot[i] = nS[i];
         }
     }
+}
+
+template <int O>
+__global__ __launch_bounds__(256) void fb_seg_carry_kernel(const double* __restrict__ rec,
+                                                           const double* __restrict__ ystate,
+                                                           double* __restrict__ segstate, int nbands,
+                                                           int nseg, long seg_tiles) {
+    fb_seg_carry_body<O>(rec, ystate, segstate, nbands, nseg, seg_tiles);
+}
+
+// the batch's carry: member blockIdx.y (grid.x covers the largest member's bands)
+template <int O>
+__global__ __launch_bounds__(256) void fb_seg_carry_many_kernel(const MixArgsMany* __restrict__ tab, long seg_tiles) {
+    const MixArgsMany* __restrict__ t = tab + blockIdx.y;
+    fb_seg_carry_body<O>(as_global(t->rec), as_global(t->ystate), as_global(t->segstate), t->nbands, t->nseg, seg_tiles);
+}
+
+// the batch's reduce: out_m[t] = sum_g partial_m[g][t] for member m = blockIdx.y, the groups summed
+// in hz::mix::slab_reduce_kernel's order (slice ty takes g = ty, ty + 4, ...; (r0 + r1) + (r2 + r3)),
+// so a member's output has the bits its own launch gives under the same segment plan
+__global__ __launch_bounds__(256) void fb_many_reduce_kernel(const MixArgsMany* __restrict__ tab) {
+    __shared__ double red[4][64];
+    const MixArgsMany* __restrict__ m = tab + blockIdx.y;
+    const double* __restrict__ slab = as_global(m->partial);
+    double* __restrict__ out = as_global(m->out);
+    const long stride = m->n_pad, n = m->n;
+    const int G = m->groups;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const long t = (long)blockIdx.x * 64 + tx;
+    double s = 0.0;
+    if (t < n)
+        for (int g = ty; g < G; g += 4) s = s + slab[(long)g * stride + t];
+    red[ty][tx] = s;
+    __syncthreads();
+    if (ty == 0 && t < n) out[t] = (red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx]);
 }
 
 // ---------------------------------------------------------------------------
@@ -762,6 +853,49 @@ static MixKernelEv pick_kernel_ev(int O, int dist, int waves, int mode) {
     }
 }
 
+// the batched form: built for what the event form is built for
+typedef void (*MixKernelMany)(const MixArgsMany*, MixArgsNone);
+typedef void (*CarryKernelMany)(const MixArgsMany*, long);
+
+template <int O, int PF>
+MixKernelMany pick_dist_many(int dist, int mode) {
+    if (mode == MODE_SEGEND) return fb_mix_kernel<O, HZ_DIST_NONE, 1, MODE_SEGEND, PF, false, true>;
+    switch (dist) {
+    case HZ_DIST_SOFTCLIP: return fb_mix_kernel<O, HZ_DIST_SOFTCLIP, 1, MODE_MIX, PF, false, true>;
+    case HZ_DIST_SATURATE: return fb_mix_kernel<O, HZ_DIST_SATURATE, 1, MODE_MIX, PF, false, true>;
+    case HZ_DIST_LIMITER: return fb_mix_kernel<O, HZ_DIST_LIMITER, 1, MODE_MIX, PF, false, true>;
+    default: return fb_mix_kernel<O, HZ_DIST_NONE, 1, MODE_MIX, PF, false, true>;
+    }
+}
+
+template <int PF>
+MixKernelMany pick_order_many(int O, int dist, int mode) {
+    switch (O) {
+    case 0: return pick_dist_many<0, PF>(dist, mode);
+    case 1: return pick_dist_many<1, PF>(dist, mode);
+    case 2: return pick_dist_many<2, PF>(dist, mode);
+    case 3: return pick_dist_many<3, PF>(dist, mode);
+    default: return pick_dist_many<4, PF>(dist, mode);
+    }
+}
+
+static MixKernelMany pick_kernel_many(int O, int dist, int waves, int mode) {
+    switch (waves) {
+    case 16: return pick_order_many<2>(O, dist, mode);
+    case 8: return pick_order_many<3>(O, dist, mode);
+    default: return pick_order_many<5>(O, dist, mode);
+    }
+}
+
+static CarryKernelMany pick_carry_many(int O) {
+    switch (O) {
+    case 1: return fb_seg_carry_many_kernel<1>;
+    case 2: return fb_seg_carry_many_kernel<2>;
+    case 3: return fb_seg_carry_many_kernel<3>;
+    default: return fb_seg_carry_many_kernel<4>;
+    }
+}
+
 static CarryKernel pick_carry(int O) {
     switch (O) {
     case 1: return fb_seg_carry_kernel<1>;
@@ -787,6 +921,34 @@ long fb_max_chunk(const hz_fb* h, bool ev = false) {
     long c = (1L << 27) / std::max(1L, G);  // doubles per row
     c = std::max<long>(kTile, (c / kTile) * kTile);
     return c;
+}
+
+// the argument block of one launch: len samples from x under plan mp, state ping-pong as it stands
+void fb_mix_args(const hz_fb* h, const double* x, long len, const hz::MixPlan& mp, MixArgs* a) {
+    a->rec = h->d_rec;
+    a->pin = h->d_pin;
+    a->gin = h->d_gin;
+    a->ystate = h->d_ystate[h->scur];
+    a->pgstate = h->d_pg[h->scur];
+    a->ystate_next = h->d_ystate[h->scur ^ 1];
+    a->pgstate_next = h->d_pg[h->scur ^ 1];
+    a->x = x;
+    a->xhist = h->d_xhist[h->xcur];
+    a->xhist_next = h->d_xhist[h->xcur ^ 1];
+    a->partial = h->d_partial;
+    a->segstate = h->d_seg;
+    a->n = len;
+    a->n_pad = mp.n_pad;
+    a->seg_len = mp.seg_len;
+    a->nseg = (int)mp.nseg;
+    a->nbands = h->N;
+    a->sp = h->sp;
+    a->sg = h->sg;
+    a->sp_tile = (double)powl((long double)h->sp, (long double)kTile);
+    a->sg_tile = (double)powl((long double)h->sg, (long double)kTile);
+    a->sp_n = (double)powl((long double)h->sp, (long double)len);
+    a->sg_n = (double)powl((long double)h->sg, (long double)len);
+    a->dist_param = h->dist_param;
 }
 
 }  // namespace
@@ -923,30 +1085,7 @@ int fb_launch_general(hz_fb* h, const double* d_in, double* d_out, long n, const
         const long nseg = mp.nseg, seg_tiles = mp.seg_tiles;
         if (nseg > 1 && O > 0) HZ_TRY(h->d_seg.reserve((size_t)h->N * nseg * O));
         MixArgsEv a;
-        a.rec = h->d_rec;
-        a.pin = h->d_pin;
-        a.gin = h->d_gin;
-        a.ystate = h->d_ystate[h->scur];
-        a.pgstate = h->d_pg[h->scur];
-        a.ystate_next = h->d_ystate[h->scur ^ 1];
-        a.pgstate_next = h->d_pg[h->scur ^ 1];
-        a.x = d_in + off;
-        a.xhist = h->d_xhist[h->xcur];
-        a.xhist_next = h->d_xhist[h->xcur ^ 1];
-        a.partial = h->d_partial;
-        a.segstate = h->d_seg;
-        a.n = len;
-        a.n_pad = mp.n_pad;
-        a.seg_len = mp.seg_len;
-        a.nseg = (int)nseg;
-        a.nbands = h->N;
-        a.sp = h->sp;
-        a.sg = h->sg;
-        a.sp_tile = (double)powl((long double)h->sp, (long double)kTile);
-        a.sg_tile = (double)powl((long double)h->sg, (long double)kTile);
-        a.sp_n = (double)powl((long double)h->sp, (long double)len);
-        a.sg_n = (double)powl((long double)h->sg, (long double)len);
-        a.dist_param = h->dist_param;
+        fb_mix_args(h, d_in + off, len, mp, &a);
         a.ev_off = ev_off;
         a.ev_rows = ev_rows;
         hipEvent_t* e = nullptr;
@@ -1015,7 +1154,14 @@ __global__ __launch_bounds__(256) void fb_tick_kernel(const double* __restrict__
     }
 }
 
-int fb_launch(hz_fb* h, const double* d_in, double* d_out, long n) {
+// hz_fb_process_many: a member whose whole call is one fb_launch_general launch at one band per
+// wave is left to the batch (fb_launch_many, then fb_many_finish) instead of launched here
+struct ManyDefer {
+    bool taken = false;
+    bool conv = false;   // for the member's fb_resp_track
+};
+
+int fb_launch(hz_fb* h, const double* d_in, double* d_out, long n, ManyDefer* defer = nullptr) {
     if (n <= 0) return HZ_OK;
     h->spare_ok = n == 1;   // one launch, one state flip: the pre-call state is the spare row
     h->last_path = HZ_FB_PATH_GENERAL;
@@ -1054,6 +1200,11 @@ int fb_launch(hz_fb* h, const double* d_in, double* d_out, long n) {
         h->last_path = HZ_FB_PATH_LTI;
         HZ_TRY(fb_launch_general(h, d_in + n_lti, d_out + n_lti, n - n_lti));
     } else {
+        if (defer && h->bands_per_wave == 1 && n <= fb_max_chunk(h)) {
+            defer->taken = true;
+            defer->conv = conv;
+            return HZ_OK;
+        }
         HZ_TRY(fb_launch_general(h, d_in, d_out, n));
     }
     return fb_resp_track(h, d_in, n, conv);
@@ -1374,6 +1525,271 @@ int hz_fb_process(hz_fb* h, const double* in, double* out, size_t n) {
     HZ_TRY(fb_launch(h, h->d_in, h->d_out, (long)n));
     HZ_TRY_HIP(hipMemcpyAsync(out, h->d_out, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
     HZ_TRY_HIP(hipStreamSynchronize(h->stream));
+    return HZ_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// hz_fb_process_many: block calls over several banks in one launch sequence
+// ---------------------------------------------------------------------------
+namespace {
+
+constexpr int kManyMax = 256;   // handles per call (the table's rows)
+
+// a member left to the batch by fb_launch: its samples after the prologue
+struct ManyItem {
+    hz_fb* h;
+    const double* in;
+    double* out;
+    long n;
+    bool conv;
+};
+
+// the batch's rows -> a device table of handles[0], through its pinned staging, on its stream; the
+// tables form a ring: the slot's last copy (kManySlots calls back) is waited for, not the last call's
+int fb_many_upload(hz_fb* lead, const std::vector<MixArgsMany>& rows, const MixArgsMany** d_tab) {
+    const size_t cap = sizeof(MixArgsMany) * kManyMax, bytes = sizeof(MixArgsMany) * rows.size();
+    const unsigned slot = lead->many_slot++ % hz_fb::kManySlots;
+    hz::Event& up = lead->many_up[slot];
+    if (!up) HZ_TRY(up.create(hipEventDisableTiming));
+    if (lead->many_up_pending[slot]) HZ_TRY_HIP(hipEventSynchronize(up));   // staging slot reuse
+    lead->many_up_pending[slot] = false;
+    HZ_TRY(lead->h_many.reserve(cap * hz_fb::kManySlots));
+    HZ_TRY(lead->d_many.reserve(cap * hz_fb::kManySlots));
+    char* hs = lead->h_many + cap * slot;
+    char* ds = lead->d_many + cap * slot;
+    std::memcpy(hs, rows.data(), bytes);
+    HZ_TRY_HIP(hipMemcpyAsync(ds, hs, bytes, hipMemcpyHostToDevice, lead->stream));
+    HZ_TRY_HIP(hipEventRecord(up, lead->stream));
+    lead->many_up_pending[slot] = true;
+    *d_tab = (const MixArgsMany*)ds;
+    return HZ_OK;
+}
+
+// One launch sequence for a batch (same order, functor id, waves, n; one band per wave; each call
+// one general launch) on handles[0]'s stream: the members' streams are ordered before and after
+// it by events, and every member's state advances as after its own fb_launch_general.
+int fb_launch_many(hz_fb* lead, const ManyItem* it, int cnt, long n) {
+    const hz_fb* f = it[0].h;   // the batch's order, functor, waves; its plan's group target
+    const int O = f->order, W = f->waves;
+    std::vector<int> groups(cnt);
+    int gmax = 0, nmax = 0;
+    for (int j = 0; j < cnt; ++j) {
+        groups[j] = fb_groups(it[j].h);
+        gmax = std::max(gmax, groups[j]);
+        nmax = std::max(nmax, it[j].h->N);
+    }
+    const hz::MixPlan mp = hz::mix_plan_batch(groups.data(), cnt, n, kTile, f->target_groups);
+    const bool segs = mp.nseg > 1 && O > 0;
+    std::vector<MixArgsMany> rows(cnt);
+    for (int j = 0; j < cnt; ++j) {
+        hz_fb* h = it[j].h;
+        HZ_TRY(h->d_partial.reserve((size_t)groups[j] * mp.n_pad));
+        if (segs) HZ_TRY(h->d_seg.reserve((size_t)h->N * mp.nseg * O));
+        fb_mix_args(h, it[j].in, n, mp, &rows[j]);
+        rows[j].out = it[j].out;
+        rows[j].groups = groups[j];
+    }
+    MixKernelMany kmix = pick_kernel_many(O, f->dist_id, W, MODE_MIX);
+    MixKernelMany kend = pick_kernel_many(O, f->dist_id, W, MODE_SEGEND);
+    HZ_TRY(hz::allow_lds(lead->device, (const void*)kmix, kLdsCeiling));
+    hipStream_t s0 = lead->stream;
+    const MixArgsMany* d_tab = nullptr;
+    HZ_TRY(fb_many_upload(lead, rows, &d_tab));
+    // the members' earlier work (their setters' uploads, their last calls) before the sequence
+    for (int j = 0; j < cnt; ++j) {
+        hz_fb* h = it[j].h;
+        if ((hipStream_t)h->stream == s0) continue;
+        if (!h->many_ready) HZ_TRY(h->many_ready.create(hipEventDisableTiming));
+        HZ_TRY_HIP(hipEventRecord(h->many_ready, h->stream));
+        HZ_TRY_HIP(hipStreamWaitEvent(s0, h->many_ready, 0));
+    }
+    hipEvent_t* e = nullptr;
+    if (lead->prof) {
+        HZ_TRY(fb_prof_events(lead, &e));
+        HZ_TRY_HIP(hipEventRecord(e[0], s0));
+    }
+    if (segs) {
+        hipLaunchKernelGGL(kend, dim3(gmax, (unsigned)(mp.nseg - 1), cnt), dim3(64 * W), lds_bytes(W, false), s0, d_tab,
+                           MixArgsNone{});
+        HZ_TRY_HIP(hipGetLastError());
+        hipLaunchKernelGGL(pick_carry_many(O), dim3((unsigned)((nmax + 255) / 256), cnt), dim3(256), 0, s0, d_tab,
+                           mp.seg_tiles);
+        HZ_TRY_HIP(hipGetLastError());
+    }
+    if (e) HZ_TRY_HIP(hipEventRecord(e[1], s0));
+    hipLaunchKernelGGL(kmix, dim3(gmax, (unsigned)mp.nseg, cnt), dim3(64 * W), lds_bytes(W, true), s0, d_tab,
+                       MixArgsNone{});
+    HZ_TRY_HIP(hipGetLastError());
+    if (e) HZ_TRY_HIP(hipEventRecord(e[2], s0));
+    if (e) HZ_TRY_HIP(hipEventRecord(e[3], s0));
+    hipLaunchKernelGGL(fb_many_reduce_kernel, dim3((unsigned)((n + 63) / 64), cnt), dim3(256), 0, s0, d_tab);
+    HZ_TRY_HIP(hipGetLastError());
+    if (e) HZ_TRY_HIP(hipEventRecord(e[4], s0));
+    lead->prof_launches += lead->prof ? 1 : 0;
+    // ... and their later work after it
+    if (!lead->many_done) HZ_TRY(lead->many_done.create(hipEventDisableTiming));
+    HZ_TRY_HIP(hipEventRecord(lead->many_done, s0));
+    for (int j = 0; j < cnt; ++j) {
+        hz_fb* h = it[j].h;
+        if ((hipStream_t)h->stream != s0) HZ_TRY_HIP(hipStreamWaitEvent(h->stream, lead->many_done, 0));
+        fb_advance(h, n);
+        ++h->many_batched;
+    }
+    return HZ_OK;
+}
+
+// the deferred members: batches by (order, functor id, waves, n) in order of appearance; a batch
+// of one is the member's own launch
+int fb_many_flush(hz_fb* lead, std::vector<ManyItem>& pend) {
+    std::vector<ManyItem> batch;
+    std::vector<char> done(pend.size(), 0);
+    for (size_t i = 0; i < pend.size(); ++i) {
+        if (done[i]) continue;
+        const hz_fb* f = pend[i].h;
+        batch.clear();
+        for (size_t j = i; j < pend.size(); ++j) {
+            const hz_fb* g = pend[j].h;
+            if (done[j] || g->order != f->order || g->dist_id != f->dist_id || g->waves != f->waves ||
+                pend[j].n != pend[i].n)
+                continue;
+            done[j] = 1;
+            batch.push_back(pend[j]);
+        }
+        if (batch.size() == 1) {
+            ++batch[0].h->many_sequential;
+            HZ_TRY(fb_launch_general(batch[0].h, batch[0].in, batch[0].out, batch[0].n));
+        } else {
+            HZ_TRY(fb_launch_many(lead, batch.data(), (int)batch.size(), pend[i].n));
+        }
+        for (const ManyItem& m : batch) HZ_TRY(fb_resp_track(m.h, m.in, m.n, m.conv));
+    }
+    pend.clear();
+    return HZ_OK;
+}
+
+// every member held: per member the prologue of hz_fb_process_device, then its own engine at once
+// or the batch at the end
+int fb_process_many_held(hz_fb* const* hs, int count, const double* d_in, long in_stride, double* d_out,
+                         long out_stride, long n) {
+    std::vector<ManyItem> pend;
+    for (int j = 0; j < count; ++j) {
+        hz_fb* h = hs[j];
+        const double* in = d_in + (long)j * in_stride;
+        double* out = d_out + (long)j * out_stride;
+        ManyDefer defer;
+        int rc = fb_block_begin(h, out, true);
+        const int k = std::max(rc, 0);
+        if (rc >= 0) rc = n - k > 0 ? fb_upload(h) : HZ_OK;
+        if (rc == HZ_OK) rc = fb_launch(h, in + k, out + k, n - k, &defer);
+        if (rc != HZ_OK) {   // the call stops here; the members before this one advance, as in the loop
+            (void)fb_many_flush(hs[0], pend);
+            return rc;
+        }
+        if (defer.taken) pend.push_back({h, in + k, out + k, n - k, defer.conv});
+        else ++h->many_sequential;
+    }
+    return fb_many_flush(hs[0], pend);
+}
+
+// the argument checks of both calls (before any handle changes); -> the handles in address order
+int fb_many_check(const char* fn, hz_fb* const* handles, int count, const void* in, long in_stride, const void* out,
+                  long out_stride, size_t n, std::vector<hz_fb*>* order) {
+    if (count < 0 || count > kManyMax) {
+        hz::set_error("%s: count %d outside [0, %d]", fn, count, kManyMax);
+        return HZ_E_INVALID;
+    }
+    if (!handles || !in || !out) {
+        hz::set_error("%s: null handle array or buffer", fn);
+        return HZ_E_INVALID;
+    }
+    for (int j = 0; j < count; ++j) {
+        if (!handles[j]) {
+            hz::set_error("%s: handle %d is null", fn, j);
+            return HZ_E_INVALID;
+        }
+        if (handles[j]->device != handles[0]->device) {
+            hz::set_error("%s: handle %d is on device %d, handle 0 on device %d", fn, j, handles[j]->device,
+                          handles[0]->device);
+            return HZ_E_INVALID;
+        }
+    }
+    if (in_stride < (long)n) {
+        hz::set_error("%s: input stride %ld below n = %zu", fn, in_stride, n);
+        return HZ_E_INVALID;
+    }
+    if (out_stride < (long)n) {
+        hz::set_error("%s: output rows overlap (stride %ld below n = %zu)", fn, out_stride, n);
+        return HZ_E_INVALID;
+    }
+    order->assign(handles, handles + count);
+    std::sort(order->begin(), order->end());
+    if (std::adjacent_find(order->begin(), order->end()) != order->end()) {
+        hz::set_error("%s: a handle appears twice", fn);
+        return HZ_E_INVALID;
+    }
+    return HZ_OK;
+}
+
+// the members after the first (address order: no lock-order inversion between callers)
+int fb_many_hold(const char* fn, const std::vector<hz_fb*>& order, std::vector<std::unique_ptr<hz_fbi::Entry>>* held) {
+    for (size_t i = 1; i < order.size(); ++i) {
+        held->emplace_back(new hz_fbi::Entry(order[i], fn, false));
+        HZ_TRY(held->back()->status);
+    }
+    return HZ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hz_fb_process_many_device(hz_fb* const* handles, int count, const double* d_in, long in_stride, double* d_out,
+                              long out_stride, size_t n) {
+    if (count == 0 || n == 0) return HZ_OK;
+    std::vector<hz_fb*> order;
+    HZ_TRY(fb_many_check("hz_fb_process_many_device", handles, count, d_in, in_stride, d_out, out_stride, n, &order));
+    hz_fb* h = order[0];
+    hz_fbi::Entry entry(h, "hz_fb_process_many_device", false);
+    HZ_TRY(entry.status);
+    std::vector<std::unique_ptr<hz_fbi::Entry>> held;
+    HZ_TRY(fb_many_hold("hz_fb_process_many_device", order, &held));
+    return fb_process_many_held(handles, count, d_in, in_stride, d_out, out_stride, (long)n);
+}
+
+int hz_fb_process_many(hz_fb* const* handles, int count, const double* in, long in_stride, double* out,
+                       long out_stride, size_t n) {
+    if (count == 0 || n == 0) return HZ_OK;
+    std::vector<hz_fb*> order;
+    HZ_TRY(fb_many_check("hz_fb_process_many", handles, count, in, in_stride, out, out_stride, n, &order));
+    hz_fb* h = order[0];
+    hz_fbi::Entry entry(h, "hz_fb_process_many", false);
+    HZ_TRY(entry.status);
+    std::vector<std::unique_ptr<hz_fbi::Entry>> held;
+    HZ_TRY(fb_many_hold("hz_fb_process_many", order, &held));
+    // all rows through handles[0]'s staging: one upload, one download; the members that run by
+    // themselves work on their own streams, so both ends are host-synchronised
+    hz_fb* lead = handles[0];
+    hipStream_t s0 = lead->stream;
+    const size_t row = sizeof(double) * n;
+    HZ_TRY(lead->d_in.reserve((size_t)count * n));
+    HZ_TRY(lead->d_out.reserve((size_t)count * n));
+    HZ_TRY_HIP(hipMemcpy2DAsync(lead->d_in, row, in, sizeof(double) * in_stride, row, count, hipMemcpyHostToDevice, s0));
+    HZ_TRY_HIP(hipStreamSynchronize(s0));
+    HZ_TRY(fb_process_many_held(handles, count, lead->d_in, (long)n, lead->d_out, (long)n, (long)n));
+    for (int j = 1; j < count; ++j)
+        if ((hipStream_t)handles[j]->stream != s0) HZ_TRY_HIP(hipStreamSynchronize(handles[j]->stream));
+    HZ_TRY_HIP(hipMemcpy2DAsync(out, sizeof(double) * out_stride, lead->d_out, row, row, count, hipMemcpyDeviceToHost, s0));
+    HZ_TRY_HIP(hipStreamSynchronize(s0));
+    return HZ_OK;
+}
+
+int hz_fb_many_info(hz_fb* h, long* batched, long* sequential) {
+    if (!h) return HZ_E_INVALID;
+    hz_fbi::HandleLock lk(h);
+    if (batched) *batched = h->many_batched;
+    if (sequential) *sequential = h->many_sequential;
     return HZ_OK;
 }
 

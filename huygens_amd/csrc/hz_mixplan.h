@@ -28,4 +28,14 @@ inline MixPlan mix_plan(long groups, long n, int tile, int target_groups) {
     return p;
 }
 
+// One launch over several banks side by side (hz_fb_process_many): the members bring their own
+// groups of partials and share n, so the plan is the one of their total group count -- a batch
+// that covers the chip with groups runs unsegmented where its members alone would not.  Every
+// member's slab is groups[j] rows of n_pad.
+inline MixPlan mix_plan_batch(const int* groups, int count, long n, int tile, int target_groups) {
+    long total = 0;
+    for (int j = 0; j < count; ++j) total += groups[j];
+    return mix_plan(std::max<long>(1, total), n, tile, target_groups);
+}
+
 }  // namespace hz

@@ -215,6 +215,12 @@ class Filterbank:
         check(self._lib.hz_fb_profile_read(self._h, C.byref(s), C.byref(m), C.byref(r), C.byref(c)))
         return s.value, m.value, r.value, c.value
 
+    def many_info(self):
+        """-> (process_many calls that took this bank in a batched launch, calls that ran it by itself)"""
+        b, q = C.c_long(), C.c_long()
+        check(self._lib.hz_fb_many_info(self._h, C.byref(b), C.byref(q)))
+        return b.value, q.value
+
     def set_path(self, path: int):
         """HZ_FB_PATH_AUTO (converged LTI engine when eligible) or HZ_FB_PATH_GENERAL."""
         check(self._lib.hz_fb_set_path(self._h, int(path)))
@@ -348,3 +354,28 @@ def sample_many(banks, x, dist: int = HZ_DIST_NONE, param: float | None = None) 
     param = dist_default_param(dist) if param is None else param
     check(lib.hz_fb_sample_many(hs, n, xs.ctypes.data_as(PD), int(dist), float(param), ys.ctypes.data_as(PD)))
     return ys
+
+
+def _handles(banks):
+    return (C.c_void_p * len(banks))(*[b._h for b in banks])
+
+
+def process_many(banks, x) -> np.ndarray:
+    """Block calls of several Filterbanks in one launch sequence where the members allow it
+    (hz_fb_process_many): out[j] = banks[j].process(x[j]) for x of shape (C, n), host buffers."""
+    c = len(banks)
+    xs = np.ascontiguousarray(x, dtype=np.float64)
+    if xs.ndim != 2 or xs.shape[0] != c:
+        raise ValueError(f"process_many: x must be of shape ({c}, n), got {xs.shape}")
+    out = np.empty_like(xs)
+    n = xs.shape[1]
+    if c and n:
+        check(banks[0]._lib.hz_fb_process_many(_handles(banks), c, dptr(xs), n, dptr(out), n, n))
+    return out
+
+
+def process_many_device(banks, x_ptr: int, x_stride: int, out_ptr: int, out_stride: int, n: int):
+    """Device pointers of planar buffers (row j at ptr + j * stride samples); the batched launches
+    run on banks[0]'s stream, every other member's stream is ordered around them by events."""
+    check(banks[0]._lib.hz_fb_process_many_device(_handles(banks), len(banks), C.c_void_p(x_ptr), int(x_stride),
+                                                  C.c_void_p(out_ptr), int(out_stride), int(n)))

@@ -111,6 +111,41 @@ int hz_fb_sample_tick(hz_fb* h);
  * 6 + count (order + 2) <= 62.  Setters on a member since its last sample, and switching a handle
  * between this call and hz_fb_sample, relaunch the server (tens of microseconds once). */
 int hz_fb_sample_many(hz_fb* const* handles, int count, const double* x, int dist_id, double param, double* y);
+/* Block calls over several Filterbanks -- the same per-channel banks at the callback's block
+ * length: what the loop  for j: hz_fb_process_device(handles[j], d_in + j in_stride,
+ * d_out + j out_stride, n)  gives, per member its output and its state (staged setters uploaded
+ * first, a cached operator() sample without tick() emitted first, path tracking, last_path, the
+ * spare ring row and the stationary history as after its own call).  The buffers are planar:
+ * channel j reads in + j in_stride and writes out + j out_stride, strides in samples and >= n.
+ * count == 0 or n == 0 is a no-op (HZ_OK); count <= 256.
+ *   Members whose whole call is one launch of the general engine at one band per wave (the
+ * smoothers still moving, or a distortion functor set) run as ONE launch sequence per batch --
+ * segment pre-pass and carry if needed, mix, reduce -- where a batch is the members that share
+ * order, distortion id (the parameter may differ), waves per workgroup and n after the cached
+ * sample; N, coefficients, targets, smoother states and k_p / k_g may differ, band shards are
+ * fine.  The segment plan is the one of the batch's total workgroup count, so a batch that
+ * fills the chip with bands skips the pre-pass its members would each need alone (outputs then
+ * agree with the loop to rounding; under equal plans, e.g. hz_fb_set_target_groups(h, 1), bit for
+ * bit).  Every other member (converged onto the LTI / stationary / streaming engine, time-sharded,
+ * tuned to several bands per wave, alone in its batch) runs by itself, as in the loop.
+ *   The sequence runs on handles[0]'s stream; every other batched member's stream is ordered
+ * before and after it by events, so earlier and later calls on the members' own streams see it.
+ * No host synchronisation beyond the one staged setters already cost.  hz_fb_profile on handles[0]
+ * counts a batched sequence as one launch.  Events and coefficient streams stay per handle
+ * (hz_fb_process_events, hz_fb_process_tv).
+ *   HZ_E_INVALID, before any handle changes: a null handle or buffer, a handle that appears twice,
+ * handles on different devices, count > 256, an input stride below n, output rows that overlap (an
+ * output stride below n).  An error raised inside one member's own prologue or launch stops the
+ * call there: the members before it in the array have advanced, as they would have in the loop,
+ * the ones after it have not.  Every member's lock is held for the call, taken in address order.
+ *   hz_fb_process_many takes host buffers: all rows go through one upload and one download on
+ * handles[0]'s stream and the call returns with the outputs in place, as hz_fb_process does.
+ * hz_fb_many_info: how many such calls took this handle in a batched launch / ran it by itself. */
+int hz_fb_process_many_device(hz_fb* const* handles, int count, const double* d_in, long in_stride,
+                              double* d_out, long out_stride, size_t n);
+int hz_fb_process_many(hz_fb* const* handles, int count, const double* in, long in_stride, double* out,
+                       long out_stride, size_t n);
+int hz_fb_many_info(hz_fb* h, long* batched, long* sequential);
 /* the number of per-sample calls served when the last setter (coefficients / boost / mix / open)
  * ran: the setter applies from that call on (setters may come from another thread while samples
  * run -- the per-sample calls and every call that touches the staged parameters, the state or

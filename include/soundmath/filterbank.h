@@ -133,4 +133,38 @@ void sample_many(Bank* const* banks, int count, const double* in, double* out, i
     detail::check(hz_fb_sample_many(hs, count, in, dist_id, param, out), "sample_many");
 }
 
+// (new) the same channels one block at a time: out row j = n x { (*F[j])(in row j [i], dist_id, param);
+// F[j]->tick(); } for planar buffers (row j at in + j * in_stride, strides in samples), the channels'
+// launches in one sequence where they allow it (hz_fb_process_many).  Each bank's pending tick()s and
+// a cached operator() sample are handled per bank, as its own process() call would.
+template <typename Bank>
+void process_many(Bank* const* banks, int count, const double* in, long in_stride, double* out, long out_stride,
+                  std::size_t n, int dist_id = HZ_DIST_NONE, double param = -1.0) {
+    if (param < 0.0) param = HZ_DIST_DEFAULT_PARAM(dist_id);
+    std::vector<hz_fb*> hs((std::size_t)count);
+    for (int j = 0; j < count; ++j) {
+        hs[(std::size_t)j] = banks[j]->native();
+        detail::check(hz_fb_set_distortion(hs[(std::size_t)j], dist_id, param), "process_many");
+    }
+    detail::check(hz_fb_process_many(hs.data(), count, in, in_stride, out, out_stride, n), "process_many");
+}
+
+// ... on the audio callback's interleaved float buffers (tests/filterbanks.cpp:196-210): channel j
+// reads in[in_frame * i + in_offset + j] and writes out[out_frame * i + out_offset + j] for i < n --
+// in_frame = CHANELS + INPUT_OFFSET, in_offset = INPUT_OFFSET, likewise for the output.  The frames are
+// deinterleaved on the host into the planar call; what the channel's input stage does before the bank
+// (the program's RMS / noise excitation) stays with the caller.
+template <typename Bank>
+void process_many_frames(Bank* const* banks, int count, const float* in, int in_frame, int in_offset, float* out,
+                         int out_frame, int out_offset, std::size_t n, int dist_id = HZ_DIST_NONE,
+                         double param = -1.0) {
+    std::vector<double> x((std::size_t)count * n), y((std::size_t)count * n);
+    for (std::size_t i = 0; i < n; ++i)
+        for (int j = 0; j < count; ++j) x[(std::size_t)j * n + i] = in[(std::size_t)in_frame * i + in_offset + j];
+    process_many(banks, count, x.data(), (long)n, y.data(), (long)n, n, dist_id, param);
+    for (std::size_t i = 0; i < n; ++i)
+        for (int j = 0; j < count; ++j)
+            out[(std::size_t)out_frame * i + out_offset + j] = (float)y[(std::size_t)j * n + i];
+}
+
 }  // namespace soundmath
